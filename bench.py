@@ -14,9 +14,12 @@ resample, reference fit, 32 mutation steps]).  `value` = particles x mutation st
 runs = particle-steps/s as SURVEY.md §8d defines it (N x number of mutation steps / wall of sample()).
 Particles are sharded over the ranks (weak scaling: 1M per GPU); all inputs are generated on the device.
 
-Same JSON line: `roofline` (the flow kernel against the fp32 MFMA peak; the pCN kernels against the HBM peak; the
-whole mutation step against both), `cpu_baseline` (the C oracle's restatement of the same mutation step on the host's
-cores, OpenMP), `extra` (IS-only temperature iteration of configs[1], the analytic-proposal runs, f32-noise variants).
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the line.  `--dump-outputs DIR`
+writes what the last timed step returned as DIR/<name>.npy (see `dump_outputs`).  `--full` adds to the same JSON line:
+`roofline` (the flow kernel against the fp32 MFMA peak; the pCN kernels against the HBM peak; the whole mutation step
+against both), `cpu_baseline` (the C oracle's restatement of the same mutation step on the host's cores, OpenMP), `extra`
+(IS-only temperature iteration of configs[1], the analytic-proposal runs, f32-noise variants); `--no-extra` and
+`--no-cpu-baseline` leave parts of it out.
 """
 from __future__ import annotations
 
@@ -155,6 +158,33 @@ def derive_limiter(sq: dict | None, hbm_frac: float | None, mfma_frac_executed: 
     return out
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(out_dir: str, sp, post) -> None:
+    """What a caller of HipSMC.sample() receives from the last timed run, as out_dir/<name>.npy (float64, or float32 where the
+    run returned float32): the particles `x` and their `log_likelihood`, `log_prior`, `log_q`, `log_w` on a fixed sample of rows
+    (default_rng(0), sorted; every row when the population fits in DUMP_BYTES), `log_evidence`, `log_evidence_error` and the
+    temperature schedule `beta`.  In a sharded run rank 0 writes the rows it holds."""
+    def host(a):
+        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+    n, d = int(post.x.shape[0]), int(post.x.shape[1])
+    n_rows = min(n, DUMP_BYTES // (d * 8 + 4 * 8))
+    rows = np.arange(n) if n_rows == n else np.sort(np.random.default_rng(0).choice(n, size=n_rows, replace=False))
+    arrays = {}
+    for name in ("x", "log_likelihood", "log_prior", "log_q", "log_w"):
+        a = getattr(post, name, None)
+        if a is not None:
+            arrays[name] = host(a[torch.as_tensor(rows, device=a.device)] if isinstance(a, torch.Tensor) else np.asarray(a)[rows])
+    arrays["log_evidence"] = np.array([float(post.log_evidence)])
+    arrays["log_evidence_error"] = np.array([float(post.log_evidence_error)])
+    arrays["beta"] = np.asarray(sp.history.beta)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def main():
     # `--gpus N` without a launcher around it: become the launcher, before anything touches the GPU
     if "WORLD_SIZE" not in os.environ:
@@ -179,15 +209,20 @@ def main():
     ap.add_argument("--mcmc-steps", type=int, default=32, help="pCN steps per temperature")
     ap.add_argument("--noise", choices=["f64", "f32"], default="f64", help="proposal-noise generator (sampler default: f64)")
     ap.add_argument("--step-fn", choices=["pcn", "tpcn"], default="pcn")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sharded-extras", action="store_true", help="N > 1: also run the extra legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed run's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the extra legs and the CPU baseline (off: only the headline)")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--sharded-extras", action="store_true", help="N > 1, --full: also run the extra legs")
     ap.add_argument("--force-sharded", action="store_true",
                     help="test rig: run the sharded code path (process group, RCCL collectives, owner layout) with a ONE-rank "
                          "group - one GPU then shows the cost of the sharded machinery itself")
     ap.add_argument("--shard-layout", choices=["owner", "slots"], default="owner",
                     help="N > 1: offspring stay on the ancestor's rank (default) or single-rank slot order with row exchange")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -260,6 +295,32 @@ def main():
     cflow = CouplingFlow(d, n_layers=4, hidden_features=(64, 64), device=eng.device, dtype=torch.float32, seed=1234)
     cflow.fit(sigma_q * 0.9 * np.random.default_rng(3).normal(size=(8000, d)), n_epochs=8)  # untimed
 
+    # The JSON line must be the LAST thing on the job's stdout.  RCCL writes a version banner through C stdio, which is
+    # flushed when a process exits - after Python's own prints: every rank flushes it now, ranks other than 0 close
+    # their stdout before the barrier, and rank 0 closes its own right after the line.
+    def emit(result):
+        def hush():
+            import ctypes
+
+            sys.stdout.flush()
+            ctypes.CDLL(None).fflush(None)
+            os.dup2(os.open(os.devnull, os.O_WRONLY), 1)
+
+        if sharded:
+            if rank != 0:
+                hush()
+            comm.barrier()
+        if rank == 0:
+            import ctypes
+
+            ctypes.CDLL(None).fflush(None)
+            print(json.dumps(result), file=record_out, flush=True)
+            hush()
+        if sharded:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+
     def sync_all():
         if sharded:
             comm.barrier()
@@ -307,6 +368,35 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = n_global * steps_done / dt
+    result = {
+        "metric": "particle-steps/sec (N x n_steps), 1M particles d=32; log-evidence err vs ref",
+        "value": value, "unit": "particle-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"configs[2]: HipSMC.sample(), {n_local} particles/GPU, d={d}, Gaussian target, RealNVP "
+                               f"coupling-flow proposal (4 layers, MLP {d // 2}->64->64->{d}, f32 on the MFMA), adaptive "
+                               f"tempering, {n_mc} {args.step_fn} steps per temperature, {args.noise} proposal noise",
+                   "step_meaning": "one bench step = one full sample() run; value counts its mutation steps "
+                                   "(N x temperatures x mcmc steps / wall)",
+                   "particles_per_gpu": n_local, "global_particles": n_global, "dims": d, "x_dtype": args.x_dtype,
+                   "flow_dtype": "f32", "flow_math": flow_math, "mcmc_steps_per_temperature": n_mc, "step_fn": args.step_fn, "noise": args.noise,
+                   "resample_mode": args.resample_mode, "resample_method": "multinomial", "beta_tolerance": 1e-6,
+                   "target_efficiency": 0.5,
+                   "parallelism": f"particle-shard x{world}" + (f" ({args.shard_layout} layout)" if sharded else "")
+                   + (" [--force-sharded rig: sharded code path over a one-rank RCCL group]" if sharded and world == 1 else "")},
+        "mutation_steps_per_run": steps_done / args.steps, "temperatures_per_run": float(np.mean(temps)),
+        "ms_per_mutation_step": dt / max(steps_done, 1) * 1e3,
+        "log_evidence": {"analytic": true_logz, "z_scores": [round(z, 3) for z in zs],
+                         "rms_z": float(np.sqrt(np.mean(np.square(zs)))), "max_abs_z": float(np.max(np.abs(zs))),
+                         "within_1_sigma_fraction": float(np.mean(np.abs(zs) <= 1.0))},
+        "mean_accept": float(np.mean(accs)),
+        "host_gc_in_timed_region": gc_headline,
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sp, post)
+    if not args.full:
+        emit(result)
+        return
 
     # ---- roofline: one more run with the library's per-kernel HIP events switched on ---------------------------------
     # (events are recorded on the launch stream around every kernel of the library; kept out of the timed region
@@ -413,32 +503,7 @@ def main():
         "mutation_share_of_gpu_time": round(step_ms * n_mut / tot_ms, 4) if tot_ms else None,
         "per_kernel": per_kernel,
     }
-
-    result = {
-        "metric": "particle-steps/sec (N x n_steps), 1M particles d=32; log-evidence err vs ref",
-        "value": value, "unit": "particle-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"configs[2]: HipSMC.sample(), {n_local} particles/GPU, d={d}, Gaussian target, RealNVP "
-                               f"coupling-flow proposal (4 layers, MLP {d // 2}->64->64->{d}, f32 on the MFMA), adaptive "
-                               f"tempering, {n_mc} {args.step_fn} steps per temperature, {args.noise} proposal noise",
-                   "step_meaning": "one bench step = one full sample() run; value counts its mutation steps "
-                                   "(N x temperatures x mcmc steps / wall)",
-                   "particles_per_gpu": n_local, "global_particles": n_global, "dims": d, "x_dtype": args.x_dtype,
-                   "flow_dtype": "f32", "flow_math": flow_math, "mcmc_steps_per_temperature": n_mc, "step_fn": args.step_fn, "noise": args.noise,
-                   "resample_mode": args.resample_mode, "resample_method": "multinomial", "beta_tolerance": 1e-6,
-                   "target_efficiency": 0.5,
-                   "parallelism": f"particle-shard x{world}" + (f" ({args.shard_layout} layout)" if sharded else "")
-                   + (" [--force-sharded rig: sharded code path over a one-rank RCCL group]" if sharded and world == 1 else "")},
-        "mutation_steps_per_run": steps_done / args.steps, "temperatures_per_run": float(np.mean(temps)),
-        "ms_per_mutation_step": dt / max(steps_done, 1) * 1e3,
-        "log_evidence": {"analytic": true_logz, "z_scores": [round(z, 3) for z in zs],
-                         "rms_z": float(np.sqrt(np.mean(np.square(zs)))), "max_abs_z": float(np.max(np.abs(zs))),
-                         "within_1_sigma_fraction": float(np.mean(np.abs(zs) <= 1.0))},
-        "mean_accept": float(np.mean(accs)),
-        "host_gc_in_timed_region": gc_headline,
-        "roofline": roofline,
-    }
+    result["roofline"] = roofline
 
     # ---- extra legs ---------------------------------------------------------------------------------------------
     if not args.no_extra and (world == 1 or args.sharded_extras):
@@ -1003,30 +1068,7 @@ def main():
             result["cpu_baseline"]["port_vs_reference"] = json.load(open(os.path.join(ROOT, "profiles", "ref_ratio.json")))
         except Exception:
             pass
-    # The JSON line must be the LAST thing on the job's stdout.  RCCL writes a version banner through C stdio, which is
-    # flushed when a process exits - after Python's own prints: every rank flushes it now, ranks other than 0 close
-    # their stdout before the barrier, and rank 0 closes its own right after the line.
-    def hush():
-        import ctypes
-
-        sys.stdout.flush()
-        ctypes.CDLL(None).fflush(None)
-        os.dup2(os.open(os.devnull, os.O_WRONLY), 1)
-
-    if sharded:
-        if rank != 0:
-            hush()
-        comm.barrier()
-    if rank == 0:
-        import ctypes
-
-        ctypes.CDLL(None).fflush(None)
-        print(json.dumps(result), file=record_out, flush=True)
-        hush()
-    if sharded:
-        import torch.distributed as dist
-
-        dist.destroy_process_group()
+    emit(result)
 
 
 if __name__ == "__main__":

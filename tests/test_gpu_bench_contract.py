@@ -1,6 +1,6 @@
 """The driver's contract with bench.py, checked on a small workload: ONE JSON line on stdout carrying the metric BASELINE.json
-names, whole-job throughput, the roofline of the dominant kernel measured in the run, the CPU baseline timed beside it, and the
-extra legs - none of which may fail silently (a leg that raised reports {"error": ...})."""
+names and whole-job throughput; with --full also the roofline of the dominant kernel measured in the run, the CPU baseline timed
+beside it, and the extra legs - none of which may fail silently (a leg that raised reports {"error": ...})."""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_roofline_cpu_baseline_and_extra_legs():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--particles-per-gpu", "262144"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--particles-per-gpu", "262144", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
     assert len(lines) == 1, lines[:3]
@@ -50,6 +50,33 @@ def test_bench_prints_one_json_line_with_roofline_cpu_baseline_and_extra_legs():
     assert legs["flow_run_maf"]["torch_ops_in_mutation_loop"] == 0
 
 
+def test_bench_plain_run_prints_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """Without --full the line carries the headline alone; --dump-outputs writes the last timed run's posterior (float32 / float64,
+    under 64 MB), and its evidence is the one behind the line's last z-score."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--particles-per-gpu", "262144", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines[:3]
+    j = json.loads(lines[0])
+    assert j["unit"] == "particle-steps/s" and j["value"] > 0 and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and len(j["log_evidence"]["z_scores"]) == 3
+    assert not {"roofline", "extra", "cpu_baseline"} & set(j)
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"x", "log_likelihood", "log_prior", "log_evidence", "log_evidence_error", "beta"} <= set(out)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    n = out["x"].shape[0]
+    assert out["x"].shape == (n, 32) and n > 0
+    assert all(out[k].shape == (n,) for k in ("log_likelihood", "log_prior", "log_q", "log_w") if k in out)
+    assert np.all(np.isfinite(out["x"])) and out["beta"][-1] == 1.0
+    z = (out["log_evidence"][0] - j["log_evidence"]["analytic"]) / out["log_evidence_error"][0]
+    assert abs(z - j["log_evidence"]["z_scores"][-1]) < 2e-3
+
+
 def test_bench_gpus_2_launches_its_own_ranks_and_reports_both():
     """`python bench.py --gpus 2` as the driver runs `--gpus 1` - no launcher around it: the process starts its own two ranks
     before any GPU call and relays rank 0's line.  One-GPU rig: both ranks on GPU 0, collectives staged
@@ -59,7 +86,7 @@ def test_bench_gpus_2_launches_its_own_ranks_and_reports_both():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--particles-per-gpu", "131072", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                        "--particles-per-gpu", "131072", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]

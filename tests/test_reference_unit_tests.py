@@ -38,7 +38,9 @@ def test_reference_unit_tests_pass_against_this_package(fname, select, at_least)
     with tempfile.TemporaryDirectory() as tmp:
         env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "tests", "tools"), PYTHONDONTWRITEBYTECODE="1")
         cmd = [sys.executable, "-m", "pytest", os.path.join(REF_TESTS, fname), "-p", "ref_alias_plugin", "-o", "addopts=",
-               "-p", "no:cacheprovider", f"--rootdir={tmp}", "-c", "/dev/null", "--import-mode=importlib", "-q", "-k", select]
+               "-p", "no:cacheprovider", f"--rootdir={tmp}", "-c", "/dev/null", "--import-mode=importlib", "-q", "-k", select,
+               # collection walks the test file's parent directories only up to here: an ordinary user may not list the ones above
+               f"--confcutdir={os.path.dirname(REF_TESTS)}"]
         out = subprocess.run(cmd, cwd=tmp, env=env, capture_output=True, text=True, timeout=900)
     tail = out.stdout[-3000:] + out.stderr[-2000:]
     assert out.returncode == 0, tail

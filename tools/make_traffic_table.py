@@ -45,7 +45,7 @@ for kind in ("bench", "kbench"):
 with open(os.path.join(ROOT, "profiles", f"{tag}_pmc_traffic.md"), "w") as fh:
     fh.write(f"# HBM traffic per launch from rocprofv3 PMC ({tag})\n\n"
              "Commands (separate passes per counter, as MI355X_MICROARCH.md §HBM prescribes), see tools/prof_round.sh:\n"
-             "`rocprofv3 --pmc FETCH_SIZE --output-format csv -- python3 bench.py --no-cpu-baseline --steps 5 --warmup 1` (bench)\n"
+             "`rocprofv3 --pmc FETCH_SIZE --output-format csv -- python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 1` (bench)\n"
              "and `... -- python3 tools/kbench.py gather pcn cdf weights flow` (kbench); the same with `--pmc WRITE_SIZE`.\n"
              "N = 1,000,000 particles, d = 32, fp64 x. Raw counters are KB, per-launch means. gfx950 correction: FETCH_SIZE\n"
              "reports half of the bytes of a wide coalesced streaming read, hence the `fetch x2` column; for the random row\n"
