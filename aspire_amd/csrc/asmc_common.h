@@ -25,18 +25,21 @@ struct asmc_ctx;
 int asmc_count_nonfinite_enqueue(asmc_ctx* ctx, int64_t n, const double* v, hipStream_t st);
 unsigned long long* asmc_count_slot(asmc_ctx* ctx);  // where the last asmc_count_nonfinite_enqueue leaves {NaN, inf} counts
 struct asmc_ctx;
-void asmc_prof_begin(asmc_ctx* ctx, const char* label, hipStream_t st);
+void asmc_prof_begin(asmc_ctx* ctx, const char* label, const void* kernel, hipStream_t st);
 void asmc_poison_lds(asmc_ctx* ctx, hipStream_t st);  // diagnostic (ASMC_POISON_LDS): every CU's LDS filled with 0xFF bytes
 void asmc_prof_end(asmc_ctx* ctx, hipStream_t st);
 #define ASMC_PROF_MAX 8192
+#define ASMC_PROF_VARIANTS 256
 // every kernel goes through this macro so that bench.py can time individual kernels with HIP events recorded on
-// the stream the kernel is launched on
+// the stream the kernel is launched on; the kernel itself (the first of the launch arguments) is logged as well, so that
+// asmc_profile_variants can name the template instantiation that ran
+#define ASMC_FIRST_ARG_(a, ...) a
 #define ASMC_LAUNCH(ctx, st, label, ...)   \
     do {                                   \
         (ctx)->rec_n = 0; /* any launch may rewrite the arrays ctx->d_rec was packed from */ \
         (ctx)->cs_n = 0;  /* ... or the scratch that holds a gather's column-sum partials */ \
         if ((ctx)->poison_lds) asmc_poison_lds((ctx), (st)); \
-        asmc_prof_begin((ctx), (label), (st)); \
+        asmc_prof_begin((ctx), (label), reinterpret_cast<const void*>(ASMC_FIRST_ARG_(__VA_ARGS__, 0)), (st)); \
         hipLaunchKernelGGL(__VA_ARGS__);   \
         asmc_prof_end((ctx), (st));        \
     } while (0)
@@ -152,6 +155,9 @@ struct asmc_ctx {
     int prof_n;
     hipEvent_t* prof_ev;        // [2 * ASMC_PROF_MAX]
     const char** prof_label;    // [ASMC_PROF_MAX]
+    int prof_nv;                                // asmc_profile_variants: distinct kernels launched since the last report
+    const void* prof_vfn[ASMC_PROF_VARIANTS];   // their host-side kernel handles
+    long long prof_vcnt[ASMC_PROF_VARIANTS];    // and launches
     // pinned host staging for scalar read-back / small uploads
     double* h_pinned;  // [8192] doubles
     unsigned ref_status_gen;  // asmc_reference_factor: generation of the pinned status cell in use (asmc_pcn.hip)

@@ -1,4 +1,5 @@
 // asmc_ctx.hip — library context, scratch allocation, error reporting.
+#include <dlfcn.h>
 #include <stdarg.h>
 
 #include <math.h>
@@ -34,8 +35,15 @@ void asmc_poison_lds(asmc_ctx* ctx, hipStream_t st) {
     hipLaunchKernelGGL(k_poison_lds, dim3(4 * ctx->num_cu), dim3(256), bytes, st, bytes / 4);
 }
 
-void asmc_prof_begin(asmc_ctx* ctx, const char* label, hipStream_t st) {
-    if (!ctx || !ctx->prof_on || ctx->prof_n >= ASMC_PROF_MAX) return;
+void asmc_prof_begin(asmc_ctx* ctx, const char* label, const void* kernel, hipStream_t st) {
+    if (!ctx || !ctx->prof_on) return;
+    int v = 0;
+    while (v < ctx->prof_nv && ctx->prof_vfn[v] != kernel) v++;
+    if (v < ASMC_PROF_VARIANTS) {
+        if (v == ctx->prof_nv) ctx->prof_vfn[v] = kernel, ctx->prof_vcnt[v] = 0, ctx->prof_nv++;
+        ctx->prof_vcnt[v]++;
+    }
+    if (ctx->prof_n >= ASMC_PROF_MAX) return;
     ctx->prof_label[ctx->prof_n] = label;
     (void)hipEventRecord(ctx->prof_ev[2 * ctx->prof_n], st);
 }
@@ -77,7 +85,29 @@ int asmc_profile_enable(asmc_ctx* ctx, int on) {
         for (int i = 0; i < 2 * ASMC_PROF_MAX; i++) ASMC_HIP(hipEventCreate(&ctx->prof_ev[i]));
     }
     ctx->prof_on = on ? 1 : 0;
-    if (on) ctx->prof_n = 0;
+    if (on) ctx->prof_n = 0, ctx->prof_nv = 0;
+    return ASMC_OK;
+}
+
+int asmc_profile_variants(asmc_ctx* ctx, char* buf, int64_t buf_len) {
+    ASMC_REQUIRE(ctx && buf && buf_len > 0, "bad arguments");
+    buf[0] = 0;
+    int64_t off = 0;
+    for (int v = 0; v < ctx->prof_nv; v++) {
+        // a kernel's host-side handle is exported under the kernel's own mangled name (an unexported one prints as its address)
+        Dl_info info;
+        const char* sym = dladdr(ctx->prof_vfn[v], &info) && info.dli_sname && info.dli_saddr == ctx->prof_vfn[v] ? info.dli_sname : nullptr;
+        char unknown[32];
+        if (!sym) snprintf(unknown, sizeof(unknown), "%p", ctx->prof_vfn[v]), sym = unknown;
+        const int w = snprintf(buf + off, (size_t)(buf_len - off), "%s %lld\n", sym, ctx->prof_vcnt[v]);
+        if (w < 0 || off + w >= buf_len) {
+            buf[off] = 0;
+            asmc_set_error("asmc_profile_variants: buffer of %lld bytes too small", (long long)buf_len);
+            return ASMC_ERR_ARG;
+        }
+        off += w;
+    }
+    ctx->prof_nv = 0;
     return ASMC_OK;
 }
 

@@ -79,16 +79,39 @@ __host__ __device__ constexpr int64_t flow16_words(int n_layers) {
 }
 
 // eight fp32 values -> their (hi, lo) fp16 operand halves; the range check rides on the hi halves (asmc_flow_dev.h)
+// The eight lo conversions are ONE asm statement whose lo registers are read-write operands holding a copy of the hi
+// pair (asmc_flow_dev.h split8_f16, TIED): the register allocator used to hand a plain output out right behind a
+// v_mfma_f32_16x16x32_f16 that reads it as SrcC - or whose D a later product has just taken as SrcC - and hipcc pads nothing
+// for an asm statement (round 6 moved one conversion away from one such product; the audit found the pattern at ~1600 other
+// places: tools/audit_asm_hazards.py).  The copies are compiler-visible writes, padded like any other; the
+// trailing s_nop 1 covers the lo registers' use as an MFMA operand.
 template <bool RELU, bool PROP = false>  // (PROP: asmc_flow_dev.h split2_f16 - NaN-propagating ReLU, no range check)
 __device__ __forceinline__ void f16_split8(const float (&x)[8], half8& hi, half8& lo, unsigned& amax_pk) {
+    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+        v[j] = !RELU ? x[j] : PROP ? __builtin_elementwise_maximum(x[j], 0.0f) : __int_as_float(max(__float_as_int(x[j]), 0));
+    half2v h[4], l[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) h[c] = half2v{(_Float16)v[2 * c], (_Float16)v[2 * c + 1]};
+#pragma unroll
+    for (int c = 0; c < 4; c++) l[c] = h[c];
+    asm("v_fma_mixlo_f16 %0, %4, -1.0, %8 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixlo_f16 %1, %5, -1.0, %10 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixlo_f16 %2, %6, -1.0, %12 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixlo_f16 %3, %7, -1.0, %14 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %0, %4, -1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %1, %5, -1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %2, %6, -1.0, %13 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %3, %7, -1.0, %15 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "s_nop 1"
+        : "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(l[3])
+        : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]),
+          "v"(v[6]), "v"(v[7]));
     unsigned hp[4], lp[4];
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
-        if (c == 3)
-            split2_f16<RELU, true, PROP>(x[2 * c], x[2 * c + 1], hp[c], lp[c]);
-        else
-            split2_f16<RELU, false, PROP>(x[2 * c], x[2 * c + 1], hp[c], lp[c]);
-    }
+    for (int c = 0; c < 4; c++) hp[c] = __builtin_bit_cast(unsigned, h[c]), lp[c] = __builtin_bit_cast(unsigned, l[c]);
     if (!PROP) {
         split4_range<!RELU>(hp[0], hp[1], amax_pk);
         split4_range<!RELU>(hp[2], hp[3], amax_pk);

@@ -264,7 +264,15 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 // `amax` collects the largest operand magnitude a lane has converted: past FLOW_HS_MAX the fp16 pair is inf / NaN and -
 // ReLU squashing NaNs - the density would come out FINITE AND WRONG, so the callers turn it into NaN (rejected and counted)
 #define FLOW_HS_MAX 65504.0f
-template <bool RELU>
+// TIED: the lo registers enter the statement as read-write operands holding a copy of the hi pair, so that the compiler
+// writes each of them (a visible copy) before the statement does.  hipcc does not check an asm statement's outputs against a
+// matrix instruction still in flight: a plain output may be handed a register right behind an MFMA that reads it as SrcC,
+// or behind one whose D a later MFMA has just taken as SrcC, and a VALU write there within the MFMA's passes corrupts the
+// product (CDNA3 ISA §7.6; tools/audit_asm_hazards.py R1 / R2).  The visible copy is padded by hipcc like any
+// other write, and the register then holds a live value up to the statement, so no MFMA in between can take it as C or D:
+// safe whatever the allocation, for one copy per packed register.  The fused flow step keeps the plain outputs (its assembly
+// is audited clean at every build, csrc/Makefile); every other caller ties them.
+template <bool RELU, bool TIED = false>
 __device__ __forceinline__ void split8_f16(const float (&x)[8], half8& hi, half8& lo, float& amax) {
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
@@ -295,18 +303,35 @@ __device__ __forceinline__ void split8_f16(const float (&x)[8], half8& hi, half8
     half2v hp[4], lp[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) hp[j] = half2v{(_Float16)v[2 * j], (_Float16)v[2 * j + 1]};
-    asm("v_fma_mixlo_f16 %0, %4, -1.0, %8 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %1, %5, -1.0, %10 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %2, %6, -1.0, %12 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %3, %7, -1.0, %14 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %0, %4, -1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %1, %5, -1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %2, %6, -1.0, %13 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %3, %7, -1.0, %15 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "s_nop 1"
-        : "=&v"(lp[0]), "=&v"(lp[1]), "=&v"(lp[2]), "=&v"(lp[3])
-        : "v"(hp[0]), "v"(hp[1]), "v"(hp[2]), "v"(hp[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]),
-          "v"(v[6]), "v"(v[7]));
+    if (TIED) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) lp[j] = hp[j];
+        asm("v_fma_mixlo_f16 %0, %4, -1.0, %8 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixlo_f16 %1, %5, -1.0, %10 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixlo_f16 %2, %6, -1.0, %12 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixlo_f16 %3, %7, -1.0, %14 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %0, %4, -1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %1, %5, -1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %2, %6, -1.0, %13 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %3, %7, -1.0, %15 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "s_nop 1"
+            : "+v"(lp[0]), "+v"(lp[1]), "+v"(lp[2]), "+v"(lp[3])
+            : "v"(hp[0]), "v"(hp[1]), "v"(hp[2]), "v"(hp[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]),
+              "v"(v[6]), "v"(v[7]));
+    } else {
+        asm("v_fma_mixlo_f16 %0, %4, -1.0, %8 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixlo_f16 %1, %5, -1.0, %10 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixlo_f16 %2, %6, -1.0, %12 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixlo_f16 %3, %7, -1.0, %14 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %0, %4, -1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %1, %5, -1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %2, %6, -1.0, %13 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %3, %7, -1.0, %15 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "s_nop 1"
+            : "=&v"(lp[0]), "=&v"(lp[1]), "=&v"(lp[2]), "=&v"(lp[3])
+            : "v"(hp[0]), "v"(hp[1]), "v"(hp[2]), "v"(hp[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]),
+              "v"(v[6]), "v"(v[7]));
+    }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         hi[2 * j] = hp[j][0];
@@ -318,7 +343,7 @@ __device__ __forceinline__ void split8_f16(const float (&x)[8], half8& hi, half8
 }
 
 // out[NBO] += Wt * act(in), `in` = NBI accumulator blocks of the previous layer (pre-activation), A = the matrix's image
-template <int NBO, int NBI, bool RELU>
+template <int NBO, int NBI, bool RELU, bool TIED = false>
 __device__ __forceinline__ void dense_from_acc_hs(floatx16 (&out)[NBO], const floatx16 (&in)[NBI], const float* __restrict__ A,
                                                   int lane, float& amax) {
     constexpr int ST = NBI * 2;  // K16 steps
@@ -329,7 +354,7 @@ __device__ __forceinline__ void dense_from_acc_hs(floatx16 (&out)[NBO], const fl
 #pragma unroll
         for (int j = 0; j < 8; j++) xv[j] = in[S / 2][8 * (S % 2) + j];
         half8 bh, bl;
-        split8_f16<RELU>(xv, bh, bl, amax);
+        split8_f16<RELU, TIED>(xv, bh, bl, amax);
         half8 ah[NBO], al[NBO];
 #pragma unroll
         for (int nbo = 0; nbo < NBO; nbo++) {
@@ -368,7 +393,7 @@ __device__ __forceinline__ void acc_bias1(floatx16 (&acc)[NB], const float* __re
 // one coupling layer of one 32-particle tile: cond / trans are the lane half's H / 2 coordinates
 // INVERSE: the sampling direction, x_b = z_b exp(s) + t (flows.py _Coupling.inverse); ladj collects -s in both directions, so
 // that base(z) + ladj is log q of the sample as well
-template <int H, int W, bool INVERSE = false, int FORM = -1>  // (FORM: see coupling_layer_hs1p)
+template <int H, int W, bool INVERSE = false, int FORM = -1, bool TIED = true>  // (FORM: see coupling_layer_hs1p; TIED: split8_f16)
 __device__ __forceinline__ void coupling_layer_hs(const float (&cond)[H / 2], float (&trans)[H / 2], const float* __restrict__ lp,
                                                   int lane, int hh, float& ladj, float& amax, int form = 0) {
     using FD = FlowDims<H, W>;
@@ -389,7 +414,7 @@ __device__ __forceinline__ void coupling_layer_hs(const float (&cond)[H / 2], fl
 #pragma unroll
             for (int j = 0; j < 8; j++) xv[j] = cond[8 * S + j];
             half8 bh, bl;
-            split8_f16<false>(xv, bh, bl, amax);
+            split8_f16<false, TIED>(xv, bh, bl, amax);
             half8 ah[FD::NB1], al[FD::NB1];
 #pragma unroll
             for (int nb = 0; nb < FD::NB1; nb++) {
@@ -410,10 +435,10 @@ __device__ __forceinline__ void coupling_layer_hs(const float (&cond)[H / 2], fl
     }
     floatx16 h2[FD::NB1];
     acc_bias1<FD::NB1>(h2, b2, hh);
-    dense_from_acc_hs<FD::NB1, FD::NB1, true>(h2, h1, A2, lane, amax);
+    dense_from_acc_hs<FD::NB1, FD::NB1, true, TIED>(h2, h1, A2, lane, amax);
     floatx16 o[FD::NB3];
     acc_bias1<FD::NB3>(o, b3, hh);
-    dense_from_acc_hs<FD::NB3, FD::NB1, true>(o, h2, A3, lane, amax);
+    dense_from_acc_hs<FD::NB3, FD::NB1, true, TIED>(o, h2, A3, lane, amax);
     flow_f2 lacc = {0.0f, 0.0f};
 #pragma unroll
     for (int q = 0; q < H / 2; q += 2)  // (form 0: s = 2 tanh(sraw / 2), see coupling_layer; pairs: flow_affine2)
@@ -444,6 +469,7 @@ typedef unsigned flow_u4 __attribute__((ext_vector_type(4)));
 // no range check at all: it converts to (hi, lo) = (+-inf, -+inf), the products with any weight - zero included - accumulate to NaN, and
 // the NaN reaches log q, where the step rejects and counts it exactly as the explicit check's NaN was.  The stand-alone density / sampling
 // kernels keep the explicit check (a sampling pass must return finite positions): same bits wherever nothing overflowed.
+// The output is a plain one (see split8_f16, TIED): only the fused flow step calls this, and the build audits its assembly.
 template <bool RELU, bool NOP = true, bool PROP = false>
 __device__ __forceinline__ void split2_f16(float x0, float x1, unsigned& hp, unsigned& lp) {
     const float v0 = !RELU ? x0 : PROP ? __builtin_elementwise_maximum(x0, 0.0f) : __int_as_float(max(__float_as_int(x0), 0));

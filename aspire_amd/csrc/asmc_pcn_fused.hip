@@ -751,9 +751,9 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
                 const float* lpk = sp + (size_t)c * FD::LAYER;
                 if (HS) {
                     if ((c & 1) == 0)
-                        coupling_layer_hs<H, W>(xa[0], xb[0], lpk, lane, hh, ladj[0], amax);
+                        coupling_layer_hs<H, W, false, -1, false>(xa[0], xb[0], lpk, lane, hh, ladj[0], amax);
                     else
-                        coupling_layer_hs<H, W>(xb[0], xa[0], lpk, lane, hh, ladj[0], amax);
+                        coupling_layer_hs<H, W, false, -1, false>(xb[0], xa[0], lpk, lane, hh, ladj[0], amax);
                 } else if ((c & 1) == 0)
                     coupling_layer<H, W, 1>(xa, xb, lpk, lane, hh, ladj);
                 else

@@ -189,6 +189,17 @@ class HipEngine:
             out[name] = (int(cnt), float(ms))
         return out
 
+    def profile_variants(self) -> dict:
+        """{mangled kernel symbol: launches} since profiling was enabled or the last call: which template instantiation of
+        each kernel ran (profile_report names the kernel family only)."""
+        buf = ctypes.create_string_buffer(1 << 16)
+        check(self.lib.asmc_profile_variants(self._ctx, buf, len(buf)), "asmc_profile_variants")
+        out = {}
+        for line in buf.value.decode().splitlines():
+            name, cnt = line.rsplit(" ", 1)
+            out[name] = out.get(name, 0) + int(cnt)
+        return out
+
     # ---- plumbing --------------------------------------------------------------------------
     @property
     def _stream(self):

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 23
+#define ASMC_ABI_VERSION 24
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -111,9 +111,12 @@ int asmc_ctx_destroy(asmc_ctx* ctx);
 
 /* Per-kernel timing with HIP events recorded on the launch stream around every kernel of the library
  * (measurement aid for bench.py's roofline leg; off by default, ~2 event records per launch when on).
- * asmc_profile_report writes lines "<kernel> <launches> <avg_ms>\n" into buf and clears the log. */
+ * asmc_profile_report writes lines "<kernel> <launches> <avg_ms>\n" into buf and clears the log.
+ * asmc_profile_variants writes lines "<mangled kernel symbol> <launches>\n", one per template instantiation launched since
+ * profiling was enabled or the last call, and clears that log (independent of asmc_profile_report's). */
 int asmc_profile_enable(asmc_ctx* ctx, int on);
 int asmc_profile_report(asmc_ctx* ctx, char* buf_host, int64_t buf_len);
+int asmc_profile_variants(asmc_ctx* ctx, char* buf_host, int64_t buf_len);
 
 /* ---- weighting / ESS / evidence (reference samples.py:1221-1249, utils.py:248-255,510-512) ---
  * Unnormalised tempered log-weight, exactly the reference association (samples.py:1222-1224):

@@ -130,6 +130,103 @@ def test_hand_issued_lds_reads_are_not_touched_before_their_waits():
     assert m and int(m.group(1)) >= 24, r.stdout
 
 
+# ---- MFMA hazards around inline asm (tools/audit_asm_hazards.py) ------------------------------------------
+def _kernel(name, body):
+    return f"\t.type\t{name},@function\n{name}:\n" + "\n".join("\t" + x if not x.endswith(":") else x for x in body) + f"\n.Lfunc_end_{name}:\n"
+
+
+_MIX = "v_fma_mixlo_f16 {}, v40, -1.0, v41 op_sel_hi:[1,0,0]"
+_M16 = "v_mfma_f32_16x16x32_f16 v[0:3], v[4:7], v[8:11], v[12:15]"  # 4 passes: SrcC WAR 3 states, D 8
+_M32 = "v_mfma_f32_32x32x16_f16 v[0:15], v[16:19], v[20:23], v[24:39]"  # 8 passes: SrcC WAR 7 states
+# rule -> (violating snippet, the same correctly padded); each violating one must fire its rule exactly once, nothing else
+HAZARD_SNIPPETS = {
+    # R1: the lo conversion written into an in-flight product's SrcC (the round-6 bug)
+    "R1": ([_M16, ";;#ASMSTART", _MIX.format("v12"), ";;#ASMEND", "s_endpgm"],
+           [_M16, ";;#ASMSTART", "s_nop 2", _MIX.format("v12"), ";;#ASMEND", "s_endpgm"]),
+    # R2: an asm read of D four states after the product issued (8 needed)
+    "R2": ([_M16, "s_nop 3", ";;#ASMSTART", "v_add_f32 v44, v0, v45", ";;#ASMEND", "s_endpgm"],
+           [_M16, "s_nop 3", ";;#ASMSTART", "s_nop 3", "v_add_f32 v44, v0, v45", ";;#ASMEND", "s_endpgm"]),
+    # R3: an asm write consumed as the B operand by the very next (compiler) MFMA
+    "R3": ([";;#ASMSTART", _MIX.format("v8"), ";;#ASMEND", _M16, "s_endpgm"],
+           [";;#ASMSTART", _MIX.format("v8"), "s_nop 1", ";;#ASMEND", _M16, "s_endpgm"]),
+    # R1 over a branch: the taken edge reaches the conversion one state after the product, the fall-through edge nine
+    "R1-branch": ([_M32, "s_cbranch_scc1 .LBB9_2", "s_nop 7", ".LBB9_2:", ";;#ASMSTART", _MIX.format("v24"), ";;#ASMEND", "s_endpgm"],
+                  [_M32, "s_nop 5", "s_cbranch_scc1 .LBB9_2", "s_nop 7", ".LBB9_2:", ";;#ASMSTART", _MIX.format("v24"), ";;#ASMEND",
+                   "s_endpgm"]),
+    # R1 around a loop: the product at the tail of the body is in flight when the back edge reaches the conversion at its head
+    "R1-loop": ([".LBB8_1:", ";;#ASMSTART", _MIX.format("v24"), ";;#ASMEND", "s_nop 4", _M32, "s_cbranch_scc1 .LBB8_1", "s_endpgm"],
+                [".LBB8_1:", ";;#ASMSTART", _MIX.format("v24"), ";;#ASMEND", "s_nop 4", _M32, "s_nop 5", "s_cbranch_scc1 .LBB8_1",
+                 "s_endpgm"]),
+}
+
+
+def test_hazard_audit_fires_each_rule_once_on_its_snippet(tmp_path):
+    """The audit's rules on hand-written assembly: each violating snippet is reported exactly once under its rule, and the same
+    snippet with the required wait states is clean (tools/audit_asm_hazards.py --self-test; no compiler needed)."""
+    import subprocess
+    import sys
+
+    paths = []
+    for rule, (bad, good) in HAZARD_SNIPPETS.items():
+        for tag, body in (("bad", bad), ("good", good)):
+            f = tmp_path / f"{rule}_{tag}.s"
+            f.write_text(_kernel(f"_Z{len(rule) + 4}{rule.replace('-', '_')}_{tag}v", body))
+            paths.append(str(f))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "audit_asm_hazards.py"), "--self-test"] + paths,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = r.stdout.splitlines()
+    for rule in HAZARD_SNIPPETS:
+        base = rule.split("-")[0]
+        bad = [x for x in lines if x.startswith(f"{rule}_bad.s:")]
+        good = [x for x in lines if x.startswith(f"{rule}_good.s:")]
+        assert len(bad) == 1 and f" {base} " in bad[0], (rule, bad)
+        assert good == [], (rule, good)
+    assert re.search(rf"{2 * len(HAZARD_SNIPPETS)} instantiations, \d+ asm statements, {len(HAZARD_SNIPPETS)} violations", lines[-1]), lines[-1]
+
+
+def test_inline_asm_next_to_mfma_keeps_its_wait_states():
+    """Every instantiation of the files that put vector instructions inside asm statements (the split-fp16 conversions of the
+    flow layers) is walked for the three MFMA hazards hipcc does not pad around an asm statement (R1 WAR on SrcC, R2 RAW / WAW
+    on D, R3 asm write -> MFMA operand); none may remain.  Compiles the three files to gfx950 assembly (no GPU; ~2-3 min)."""
+    import shutil
+    import subprocess
+    import sys
+
+    if not shutil.which("hipcc") and not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "audit_asm_hazards.py"), "--jobs", "3"], capture_output=True,
+                       text=True, timeout=1800)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    m = re.search(r"(\d+) instantiations, (\d+) asm statements, 0 violations", r.stdout)
+    assert m and int(m.group(1)) >= 280 and int(m.group(2)) >= 5000, r.stdout[-3000:]
+
+
+def test_every_source_with_vector_asm_is_audited():
+    """tools/audit_asm_hazards.py SOURCES must list every translation unit that reaches an asm statement holding a vector
+    instruction (directly or through the csrc headers)."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("audit_asm_hazards", os.path.join(ROOT, "tools", "audit_asm_hazards.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    csrc = os.path.join(ROOT, "aspire_amd", "csrc")
+
+    def has_vector_asm(text):
+        return any(re.search(r"\bv_[a-z]", m) for m in re.findall(r"\basm\s*(?:volatile\s*)?\(((?:[^;]|;(?!\s*$))*?)\)\s*;", text, re.S | re.M))
+
+    def reaches(path, seen):
+        if path in seen or not os.path.exists(path):
+            return False
+        seen.add(path)
+        text = open(path).read()
+        return has_vector_asm(text) or any(reaches(os.path.join(csrc, h), seen) for h in re.findall(r'#include "([^"]+)"', text))
+
+    need = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and reaches(os.path.join(csrc, f), set()))
+    assert "asmc_flow16.hip" in need
+    assert sorted(mod.SOURCES) == need
+
+
 def test_flow_packing_places_every_weight_once():
     """asmc_coupling_pack / asmc_maf_pack are host-only (no GPU): the MFMA operand image is a permutation of the layers' weights and
     biases padded with zeros - coupling flow at a padded dimension, autoregressive flow at an odd one (its MADE masks leave zeros in
