@@ -26,7 +26,7 @@ COUNT_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 ASMC_BIS_REC = 40
 ASMC_SELECT_THREADS = 262144
 ASMC_STUDENT_MAX_ROWS = 16384
-ASMC_ABI_VERSION = 24
+ASMC_ABI_VERSION = 25
 ASMC_FLOW_COUPLING, ASMC_FLOW_MAF = 0, 1  # asmc_coupling.kind
 ASMC_MAX_COUNT_CELLS = 64  # asmc_pcn_set_count_cells
 ASMC_CDF_REC = 9
@@ -217,6 +217,12 @@ SIGNATURES = {
         [_vp, _i64, _vp, _vp, _vp, _vp, POINTER(AsmcPcnParams), POINTER(AsmcCoupling), _vp, _i64, _i, _u32, _d, _vp],
     ),
     "asmc_pcn_mutate_flow_result": (_i, [_vp, _i, _pd, _pi64, _pd, _vp]),
+    "asmc_stretch_propose": (_i, [_vp, _i64, _i, _i, _vp, _i, _d, _u64, _u32, _u32, _i, _vp, _vp, _vp]),
+    "asmc_stretch_accept": (
+        _i,
+        [_vp, _i64, _i, _i, _vp, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _i, _vp],
+    ),
+    "asmc_stretch_counts": (_i, [_vp, _i, _pi64, _vp]),
 }
 
 _lib = None

@@ -1155,3 +1155,37 @@ class HipEngine:
         check(self.lib.asmc_pcn_split_end(self._ctx, n_steps, n_acc.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _f64p(hist),
                                           ctypes.byref(rho), self._stream), "asmc_pcn_split_end")
         return n_acc, hist, rho.value
+
+    # ---- stretch move of the "emcee_smc" sampler (include/asmc.h asmc_stretch_*) -------------------------------------------
+    def stretch_propose(self, x, half: int, a: float, seed: int, shard: int, step: int, t: int):
+        """Half-sweep `half` of step `step`: (y [|half|, d] in x's dtype, logf [|half|] = (d - 1) log zz).  `t`: the step's index
+        in the mutation's count array (half 0 zeroes that counter)."""
+        n, d = x.shape
+        m = (n + 1 - half) // 2
+        y = torch.empty((m, d), dtype=x.dtype, device=x.device)
+        logf = self.empty(m)
+        check(self.lib.asmc_stretch_propose(self._ctx, n, d, self._xdt(x), _dptr(x), int(half), float(a), int(seed), int(shard),
+                                            int(step), int(t), _dptr(y), _dptr(logf), self._stream), "asmc_stretch_propose")
+        return y, logf
+
+    def stretch_accept(self, x, half: int, y, logf, beta: float, ll, lp, lq, ll_new, lp_new, lq_new, seed: int, shard: int,
+                       step: int, t: int, logj=None, logj_new=None):
+        """Accepts the proposals of `stretch_propose` in place (rows of x, carried densities; logj / logj_new: carried / proposed
+        log-Jacobian of a chain in a preconditioned space, both or neither); the count stays on the device."""
+        self._chk3(ll, lp, lq)
+        n, d = x.shape
+        ll_new, lp_new, lq_new = (v.to(torch.float64).contiguous() for v in (ll_new, lp_new, lq_new))
+        if logj is not None:
+            assert logj.dtype == torch.float64 and logj.is_contiguous()
+            logj_new = logj_new.to(torch.float64).contiguous()
+        check(self.lib.asmc_stretch_accept(self._ctx, n, d, self._xdt(x), _dptr(x), int(half), _dptr(y), _dptr(logf), float(beta),
+                                           _dptr(ll), _dptr(lp), _dptr(lq), _dptr(logj), _dptr(ll_new), _dptr(lp_new), _dptr(lq_new),
+                                           _dptr(logj_new), int(seed), int(shard), int(step), int(t), self._stream),
+              "asmc_stretch_accept")
+
+    def stretch_counts(self, n_steps: int) -> np.ndarray:
+        """Accept counts of step indices 0 .. n_steps - 1 (this rank's walkers) - synchronises."""
+        out = np.zeros(n_steps, dtype=np.int64)
+        check(self.lib.asmc_stretch_counts(self._ctx, int(n_steps), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream),
+              "asmc_stretch_counts")
+        return out

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 24
+#define ASMC_ABI_VERSION 25
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -737,6 +737,40 @@ int asmc_transform_inverse(asmc_ctx* ctx, int64_t n, int x_dtype, const void* z_
 int asmc_pcn_ysplit_propose_tr(asmc_ctx* ctx, int64_t n, const asmc_pcn_params* prm, uint32_t step, const asmc_transform* t,
                                const double* premap_dev, const asmc_mixture* qmix, int minus_logj, void* x_prop_dev,
                                double* logj_out_dev, double* lq_out_dev, asmc_stream stream);
+
+/* ---- affine-invariant ensemble move of the "emcee_smc" sampler (ABI 25) ------------------------------------------------
+ * Replaces emcee's EnsembleSampler.run_mcmc inside EmceeSMC.mutate (reference src/aspire/samplers/smc/emcee.py:47-89): emcee's
+ * default move, StretchMove(a) on RedBlueMove(nsplits = 2, randomize_split = True) (Goodman & Weare 2010), over an ensemble of
+ * the n walkers of x_dev [n, d] (this rank's shard; x_dtype), on the tempered log-target of smc/base.py:507-519.  A step t is two
+ * half-sweeps h = 0 then 1, each  asmc_stretch_propose -> (caller: densities at y) -> asmc_stretch_accept;  asmc_stretch_counts
+ * reads the accept counts of a mutation's steps once at its end (synchronises).  emcee itself is absent: no parity with its
+ * numpy random stream.
+ * Split (a pure function of seed, shard, step): a bijection sigma of [0, n), n >= 2 - a Feistel network on 2 H bits,
+ *   H = ceil(B / 2), B = ceil(log2 n), walked until the value falls inside [0, n) (cycle walking).  One pass of the network:
+ *   v = (L << H) | R; rounds r = 0 .. 3: (L, R) <- (R, L ^ F_r(R)); F_r(R) = w[0] & (2^H - 1) of
+ *   Philox4x32-10(counter {R, step, r, 0xA0000000 | shard}, key {seed lo, seed hi}).  sigma^-1 runs the rounds backwards.
+ *   Walker i is in half sigma(i) & 1: half 0 holds ceil(n / 2) walkers, half 1 floor(n / 2).  Slot m of half h is the walker
+ *   k = sigma^-1(2 m + h).
+ * Draws of slot m of half h at step `step`: block b = Philox4x32-10(counter {m, step, 2 b + h, 0x60000000 | shard}, key as above);
+ *   b = 0: u = U(w[0], w[1]) (stretch variate), u' = U(w[2], w[3]) (accept variate), U(hi, lo) = ((hi << 21 ^ lo >> 11) & (2^53 - 1)
+ *   + 0.5) / 2^53;  b = 1: m' = floor(((w[0] << 32) | w[1]) * S_o / 2^64), S_o = (n + h) / 2 walkers in the other half, and the
+ *   complementary walker j = sigma^-1(2 m' + 1 - h).
+ * asmc_stretch_propose: for the S_h = (n + 1 - h) / 2 slots of half h: zz = ((a - 1) u + 1)^2 / a, y_dev[m, :] = x_j - (x_j - x_k) zz
+ *   (fp64 arithmetic in this order, rounded to x_dtype; y_dev is [S_h, d] in x_dtype) and logf_dev[m] = (d - 1) log zz.  Half 0
+ *   also zeroes the counter of step index t (0 <= t < 2048, the step's place in the mutation's count array).  a > 1.
+ * asmc_stretch_accept: for slot m: lnpdiff = (logf[m] + L(ll_new, lp_new, lq_new [, lj_new])[m]) - L(ll, lp, lq [, lj])[k], with
+ *   L = (1 - beta) lq + beta (ll + lp) [+ log|det J|] and NaN / +inf -> -inf (as every accept entry point, above); accepted iff
+ *   lnpdiff > log u'.  Accepted: row k of x_dev <- y_dev[m], ll / lp / lq / lj [k] <- the new values [m]; the accepts are added
+ *   to the counter of step index t.  lj_dev / lj_new_dev (both or NULL): carried / proposed log|det dT^-1/dz| of a chain in a
+ *   preconditioned space.  Only the rows of half h are written; the next half-sweep reads them in stream order.
+ * asmc_stretch_counts: counts_host[0 .. n_steps) <- the accept counts of step indices 0 .. n_steps - 1 (local walkers). */
+int asmc_stretch_propose(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x_dev, int half, double a, uint64_t seed,
+                         uint32_t shard, uint32_t step, int t, void* y_dev, double* logf_dev, asmc_stream stream);
+int asmc_stretch_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x_dev, int half, const void* y_dev,
+                        const double* logf_dev, double beta, double* ll_dev, double* lp_dev, double* lq_dev, double* lj_dev,
+                        const double* ll_new_dev, const double* lp_new_dev, const double* lq_new_dev, const double* lj_new_dev,
+                        uint64_t seed, uint32_t shard, uint32_t step, int t, asmc_stream stream);
+int asmc_stretch_counts(asmc_ctx* ctx, int n_steps, int64_t* counts_host, asmc_stream stream);
 
 #ifdef __cplusplus
 }
