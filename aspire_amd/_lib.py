@@ -26,7 +26,7 @@ COUNT_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 ASMC_BIS_REC = 40
 ASMC_SELECT_THREADS = 262144
 ASMC_STUDENT_MAX_ROWS = 16384
-ASMC_ABI_VERSION = 25
+ASMC_ABI_VERSION = 26
 ASMC_FLOW_COUPLING, ASMC_FLOW_MAF = 0, 1  # asmc_coupling.kind
 ASMC_MAX_COUNT_CELLS = 64  # asmc_pcn_set_count_cells
 ASMC_CDF_REC = 9
@@ -223,6 +223,20 @@ SIGNATURES = {
         [_vp, _i64, _i, _i, _vp, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _i, _vp],
     ),
     "asmc_stretch_counts": (_i, [_vp, _i, _pi64, _vp]),
+    "asmc_rw_propose": (_i, [_vp, _i64, _i, _i, _vp, _i, _d, _vp, _u64, _u64, _u32, _i, _vp, _vp]),
+    "asmc_mh_accept": (_i, [_vp, _i64, _i, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _i, _vp]),
+    "asmc_mh_counts": (_i, [_vp, _i, _pi64, _vp]),
+    "asmc_hmc_momentum": (_i, [_vp, _i64, _i, _vp, _u64, _u64, _u32, _i, _vp, _vp]),
+    "asmc_hmc_leap": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _d, _d, _vp]),
+    "asmc_hmc_accept": (
+        _i,
+        [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _i, _vp, _vp, _vp],
+    ),
+    "asmc_hmc_mix": (
+        _i,
+        [_vp, _i64, _i, _vp, _vp, _vp, _vp, _d, POINTER(AsmcMixture), POINTER(AsmcMixture), POINTER(AsmcMixture), _vp, _d, _i, _u64,
+         _u64, _u32, _i, _i, _vp, _vp],
+    ),
 }
 
 _lib = None

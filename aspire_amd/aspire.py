@@ -2,7 +2,7 @@
 
 Kept: constructor keywords (aspire.py:79-98), `fit`, `sample_posterior` (signature, kwargs routing by
 `inspect.signature`, `return_history`, `n_likelihood_evaluations`), `get_sampler_class`,
-`init_sampler`.  `sampler in {"smc", "minipcn_smc", "emcee_smc"}` is implemented natively (the hot path this
+`init_sampler`.  `sampler in {"smc", "minipcn_smc", "emcee_smc", "blackjax_smc"}` is implemented natively (the hot path this
 repository replaces); other names resolve through the `aspire.samplers` entry-point group exactly
 like the reference (aspire.py:293-304) and otherwise raise.  HDF5 checkpoint files, plotting and
 the JAX backend are out of scope.
@@ -307,6 +307,8 @@ class Aspire:
             from .samplers.smc import HipSMC as SamplerClass
         elif sampler_type == "emcee_smc":
             from .samplers.emcee_smc import HipEmceeSMC as SamplerClass
+        elif sampler_type == "blackjax_smc":
+            from .samplers.blackjax_smc import HipBlackJAXSMC as SamplerClass
         else:
             from importlib.metadata import entry_points
 
@@ -530,7 +532,7 @@ class Aspire:
         self._resume_from_default = data["state_path"]
         self._resume_sampler_type = sampler or data.get("sampler_type") or (state.get("sampler") if isinstance(state, dict) else None)
         # (a state records the class name, `sample_posterior` takes the registry name)
-        self._resume_sampler_type = {"HipSMC": "smc", "HipEmceeSMC": "emcee_smc"}.get(self._resume_sampler_type, self._resume_sampler_type)
+        self._resume_sampler_type = {"HipSMC": "smc", "HipEmceeSMC": "emcee_smc", "HipBlackJAXSMC": "blackjax_smc"}.get(self._resume_sampler_type, self._resume_sampler_type)
         self._resume_n_samples = data.get("n_samples")
         self._resume_overrides = dict(resume_kwargs or {})
         self._resume_sampler_config = {k: v for k, v in (data.get("sampler_config") or {}).items() if k != "sampler_class"}

@@ -116,6 +116,7 @@ struct asmc_ctx {
     long long* d_counts;           // [ASMC_MAX_PCN_STEPS + max(ASMC_MAX_BLOCKS, n_max/64+1)] accept counts / partials
     double* d_rho;                 // [ASMC_MAX_PCN_STEPS + 8] step-size history on device
     unsigned long long* d_stretch; // [ASMC_MAX_PCN_STEPS] accept counts of the steps of a stretch-move mutation (asmc_stretch.hip)
+    unsigned long long* d_mh;      // [ASMC_MAX_PCN_STEPS] accept counts of the steps of a random-walk / HMC mutation (asmc_hmc.hip)
     unsigned int* d_tilectr;       // [2 * ASMC_MAX_PCN_STEPS + 2] fused flow-proposal step: tile hand-out counters, blocks-done counters (one each per step), non-finite density count (64-bit)
     unsigned int* d_bar;           // [1024 * 17] arrival counters + the poison cell of the persistent importance-weight kernel's grid barriers (4 KB apart; they only grow)
     unsigned int bar_base[17];     // their values when the next launch starts (top, groups)

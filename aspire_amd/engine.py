@@ -1189,3 +1189,84 @@ class HipEngine:
         check(self.lib.asmc_stretch_counts(self._ctx, int(n_steps), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream),
               "asmc_stretch_counts")
         return out
+
+    # ---- random-walk MH and HMC of the "blackjax_smc" sampler (include/asmc.h asmc_rw_* / asmc_mh_* / asmc_hmc_*) ---------------
+    def rw_propose(self, x, sigma, seed: int, gid0: int, step: int, t: int):
+        """y = x + sigma xi in x's dtype.  `sigma`: a float (standard deviation), a device [d] tensor (per-coordinate standard
+        deviations) or a device [d, d] tensor (lower-triangular factor of a covariance).  Zeroes the counter of step index `t`."""
+        n, d = x.shape
+        y = torch.empty_like(x)
+        if isinstance(sigma, torch.Tensor):
+            assert sigma.dtype == torch.float64 and sigma.is_contiguous() and sigma.shape in ((d,), (d, d))
+            mode, scalar, sig = sigma.dim(), 0.0, sigma
+        else:
+            mode, scalar, sig = 0, float(sigma), None
+        check(self.lib.asmc_rw_propose(self._ctx, n, d, self._xdt(x), _dptr(x), mode, scalar, _dptr(sig), int(seed), int(gid0),
+                                       int(step), int(t), _dptr(y), self._stream), "asmc_rw_propose")
+        return y
+
+    def mh_accept(self, x, y, beta: float, ll, lp, lq, ll_new, lp_new, lq_new, seed: int, gid0: int, step: int, t: int, logj=None,
+                  logj_new=None):
+        """Symmetric Metropolis-Hastings accept of the proposals `y` in place (rows of x, carried densities; logj / logj_new as in
+        `stretch_accept`); the count stays on the device."""
+        self._chk3(ll, lp, lq)
+        n, d = x.shape
+        ll_new, lp_new, lq_new = (v.to(torch.float64).contiguous() for v in (ll_new, lp_new, lq_new))
+        if logj is not None:
+            assert logj.dtype == torch.float64 and logj.is_contiguous()
+            logj_new = logj_new.to(torch.float64).contiguous()
+        check(self.lib.asmc_mh_accept(self._ctx, n, d, self._xdt(x), _dptr(x), _dptr(y), float(beta), _dptr(ll), _dptr(lp), _dptr(lq),
+                                      _dptr(logj), _dptr(ll_new), _dptr(lp_new), _dptr(lq_new), _dptr(logj_new), int(seed), int(gid0),
+                                      int(step), int(t), self._stream), "asmc_mh_accept")
+
+    def mh_counts(self, n_steps: int) -> np.ndarray:
+        """Accept counts of step indices 0 .. n_steps - 1 (this rank's particles) - synchronises."""
+        out = np.zeros(n_steps, dtype=np.int64)
+        check(self.lib.asmc_mh_counts(self._ctx, int(n_steps), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream),
+              "asmc_mh_counts")
+        return out
+
+    def hmc_momentum(self, n: int, d: int, minv, seed: int, gid0: int, step: int, t: int):
+        """p [n, d] ~ N(0, M), M^-1 = diag(minv) (None: identity).  Zeroes the counter of step index `t`."""
+        p = self.empty((n, d))
+        check(self.lib.asmc_hmc_momentum(self._ctx, n, d, _dptr(minv), int(seed), int(gid0), int(step), int(t), _dptr(p), self._stream),
+              "asmc_hmc_momentum")
+        return p
+
+    def hmc_leap(self, z, p, g, minv, kick: float, drift: float):
+        """p += kick g; z += drift minv p, in place (fp64 [n, d])."""
+        for v in (z, p, g):
+            assert v.dtype == torch.float64 and v.is_contiguous() and v.shape == z.shape
+        n, d = z.shape
+        check(self.lib.asmc_hmc_leap(self._ctx, n, d, _dptr(z), _dptr(p), _dptr(g), _dptr(minv), float(kick), float(drift), self._stream),
+              "asmc_hmc_leap")
+
+    def hmc_accept(self, x, z_new, p0, p1, minv, beta: float, ll, lp, lq, ll_new, lp_new, lq_new, seed: int, gid0: int, step: int,
+                   t: int, ke0=None, ke1=None, want_dH: bool = False):
+        """HMC accept on dH = [log p_t(new) - K1] - [log p_t(old) - K0] in place (rows of x <- z_new, carried densities); K from
+        the momenta p0 / p1 unless ke0 / ke1 are given.  Returns (accept flags [n] bool, dH [n] or None)."""
+        self._chk3(ll, lp, lq)
+        n, d = x.shape
+        assert z_new.dtype == torch.float64 and z_new.is_contiguous() and z_new.shape == x.shape
+        ll_new, lp_new, lq_new = (v.to(torch.float64).contiguous() for v in (ll_new, lp_new, lq_new))
+        flags = torch.empty(n, dtype=torch.uint8, device=self.device)
+        dH = self.empty(n) if want_dH else None
+        check(self.lib.asmc_hmc_accept(self._ctx, n, d, self._xdt(x), _dptr(x), _dptr(z_new), _dptr(p0), _dptr(p1), _dptr(minv),
+                                       _dptr(ke0), _dptr(ke1), float(beta), _dptr(ll), _dptr(lp), _dptr(lq), _dptr(ll_new),
+                                       _dptr(lp_new), _dptr(lq_new), int(seed), int(gid0), int(step), int(t), _dptr(flags), _dptr(dH),
+                                       self._stream), "asmc_hmc_accept")
+        return flags.bool(), dH
+
+    def hmc_mix(self, x, ll, lp, lq, beta: float, t_ll: DeviceMixture, t_lp: DeviceMixture, t_lq: DeviceMixture, minv, step_size: float,
+                n_leap: int, seed: int, gid0: int, step0: int, n_steps: int, t0: int = 0, want_dH: bool = False):
+        """Transitions step0 .. step0 + n_steps - 1 of HMC on three built-in mixtures in one launch, in place (fp64 rows, d <= 128;
+        counters t0 .. t0 + n_steps - 1).  Returns the last transition's dH [n] when asked for."""
+        self._chk3(ll, lp, lq)
+        assert x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 2
+        n, d = x.shape
+        dH = self.empty(n) if want_dH else None
+        cs = [m.c_struct() for m in (t_ll, t_lp, t_lq)]
+        check(self.lib.asmc_hmc_mix(self._ctx, n, d, _dptr(x), _dptr(ll), _dptr(lp), _dptr(lq), float(beta), ctypes.byref(cs[0]),
+                                    ctypes.byref(cs[1]), ctypes.byref(cs[2]), _dptr(minv), float(step_size), int(n_leap), int(seed),
+                                    int(gid0), int(step0), int(n_steps), int(t0), _dptr(dH), self._stream), "asmc_hmc_mix")
+        return dH

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 25
+#define ASMC_ABI_VERSION 26
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -771,6 +771,59 @@ int asmc_stretch_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x_de
                         const double* ll_new_dev, const double* lp_new_dev, const double* lq_new_dev, const double* lj_new_dev,
                         uint64_t seed, uint32_t shard, uint32_t step, int t, asmc_stream stream);
 int asmc_stretch_counts(asmc_ctx* ctx, int n_steps, int64_t* counts_host, asmc_stream stream);
+
+/* ---- random-walk Metropolis-Hastings and HMC mutations of the "blackjax_smc" sampler (ABI 26) --------------------------------
+ * Replace blackjax.rmh / blackjax.hmc inside BlackJAXSMC.mutate (reference src/aspire/samplers/smc/blackjax.py:145-349): one
+ * independent chain per particle on the tempered log-target of smc/base.py:507-519.  blackjax and jax are absent: no parity with
+ * their random streams.
+ * Streams: particle i of this rank has the global id gid = gid0 + i and the pCN streams under the mutation's key `seed`:
+ *   normals of coordinates 4 q .. 4 q + 3 at transition `step`: the four variates of the Philox4x32-10 block with counter
+ *     {gid lo, gid hi, step, q | 0x20000000} (words (w0, w1) -> coordinates 4 q, 4 q + 1, (w2, w3) -> 4 q + 2, 4 q + 3; radius from
+ *     u = (w_r + 1/2) 2^-32, angle t = (w_a + 1/2) 2^-32 turns, (z_even, z_odd) = sqrt(-2 ln u) (cos, sin)(2 pi t));
+ *   accept variate: u' = U(w[0], w[1]) of the block with counter {gid lo, gid hi, step, 0xFFFFFFFF}.
+ *   The slot tags are pCN's: the key differs per mutation, so no two draws of a run share (key, counter).  Keying by the global
+ *   id makes a sharded run draw what a single-rank run draws for the same population.
+ * Counters: the accepts of a transition go to the device-resident counter of its step index t (0 <= t < 2048, the transition's
+ *   place in the current chunk); asmc_rw_propose and asmc_hmc_momentum zero counter t (a step's first launch), asmc_hmc_mix zeroes
+ *   counters t0 .. t0 + n_steps - 1 itself; asmc_mh_counts reads counters 0 .. n_steps - 1 back (synchronises).
+ * asmc_rw_propose: y_dev [n, d] (x_dtype) <- x + s xi in fp64, rounded to x_dtype.  sigma_mode 0: s = sigma (scalar standard
+ *   deviation); 1: s = sig_dev[c] (per-coordinate standard deviations); 2: y = x + L xi with L = sig_dev [d, d] row-major, its lower
+ *   triangle read (the Cholesky factor of a proposal covariance).
+ * asmc_mh_accept: accept iff L(ll_new, lp_new, lq_new [, lj_new])[i] - L(ll, lp, lq [, lj])[i] > log u', L as in
+ *   asmc_stretch_accept (NaN / +inf -> -inf).  Accepted: row i of x_dev <- y_dev[i], ll / lp / lq / lj [i] <- the new values.
+ * asmc_hmc_momentum: p_dev [n, d] (fp64) <- xi_c / sqrt(minv_dev[c]), p ~ N(0, M) with M^-1 = diag(minv_dev); NULL: identity.
+ * asmc_hmc_leap: p += kick g; z += drift minv p (all [n, d] fp64, in this order: z moves with the updated p).  A velocity-Verlet
+ *   trajectory of L steps of size e is leap(e/2, e), then L - 1 times (gradient; leap(e, e)), then (gradient; leap(e/2, 0)).
+ * asmc_hmc_accept: dH = [L(new)[i] - K1] - [L(old)[i] - K0], K = ke0_dev / ke1_dev [i] when given, else 1/2 sum_c minv_c p_c^2 of
+ *   p0_dev / p1_dev; accept iff log u' < dH (a NaN dH and a proposal whose L is NaN / +inf are rejections).  Accepted: row i of
+ *   x_dev (x_dtype) <- z_new_dev[i] (fp64, rounded), ll / lp / lq [i] <- the new values.  flags_dev [n] (bytes) and dH_out_dev [n]
+ *   are optional outputs.
+ * asmc_hmc_mix: transitions step0 .. step0 + n_steps - 1 of HMC (n_leap velocity-Verlet steps of size step_size, diagonal inverse
+ *   mass minv_dev or NULL) in ONE launch for three diagonal Gaussian mixtures: L = (1 - beta) log_q + beta (log_likelihood +
+ *   log_prior), value and gradient in closed form; fp64 state, d <= 128.  Rows and carried densities are read / written once per
+ *   launch; the energy of the start point uses the densities recomputed at x (the carried arrays are outputs only: rows that never
+ *   move keep theirs bit for bit); an accepted row carries the densities of its trajectory's last gradient evaluation.
+ *   dH_out_dev [n] (optional): dH of the last transition. */
+int asmc_rw_propose(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x_dev, int sigma_mode, double sigma,
+                    const double* sig_dev, uint64_t seed, uint64_t gid0, uint32_t step, int t, void* y_dev, asmc_stream stream);
+int asmc_mh_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x_dev, const void* y_dev, double beta, double* ll_dev,
+                   double* lp_dev, double* lq_dev, double* lj_dev, const double* ll_new_dev, const double* lp_new_dev,
+                   const double* lq_new_dev, const double* lj_new_dev, uint64_t seed, uint64_t gid0, uint32_t step, int t,
+                   asmc_stream stream);
+int asmc_mh_counts(asmc_ctx* ctx, int n_steps, int64_t* counts_host, asmc_stream stream);
+int asmc_hmc_momentum(asmc_ctx* ctx, int64_t n, int d, const double* minv_dev, uint64_t seed, uint64_t gid0, uint32_t step, int t,
+                      double* p_dev, asmc_stream stream);
+int asmc_hmc_leap(asmc_ctx* ctx, int64_t n, int d, double* z_dev, double* p_dev, const double* g_dev, const double* minv_dev,
+                  double kick, double drift, asmc_stream stream);
+int asmc_hmc_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x_dev, const double* z_new_dev, const double* p0_dev,
+                    const double* p1_dev, const double* minv_dev, const double* ke0_dev, const double* ke1_dev, double beta,
+                    double* ll_dev, double* lp_dev, double* lq_dev, const double* ll_new_dev, const double* lp_new_dev,
+                    const double* lq_new_dev, uint64_t seed, uint64_t gid0, uint32_t step, int t, unsigned char* flags_dev,
+                    double* dH_out_dev, asmc_stream stream);
+int asmc_hmc_mix(asmc_ctx* ctx, int64_t n, int d, void* x_dev, double* ll_dev, double* lp_dev, double* lq_dev, double beta,
+                 const asmc_mixture* log_likelihood, const asmc_mixture* log_prior, const asmc_mixture* log_q,
+                 const double* minv_dev, double step_size, int n_leap, uint64_t seed, uint64_t gid0, uint32_t step0, int n_steps,
+                 int t0, double* dH_out_dev, asmc_stream stream);
 
 #ifdef __cplusplus
 }
