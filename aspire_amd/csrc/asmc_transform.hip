@@ -160,7 +160,6 @@ static int launch_transform(asmc_ctx* ctx, int64_t n, const T* in, T* out, doubl
     int wpb = ASMC_BLOCK / 64;
     while (wpb > 1 && per_wave * wpb > 64 * 1024) wpb >>= 1;
     const size_t lds = per_wave * wpb;
-    ASMC_REQUIRE(lds <= 64 * 1024, "row too long for one LDS tile");
     const int64_t n_tiles = (n + 63) / 64;
     const int grid = grid_for(n_tiles, wpb, ctx->num_cu * 8);
     const uintptr_t a = (uintptr_t)in | (uintptr_t)out;
@@ -192,6 +191,8 @@ static int launch_transform(asmc_ctx* ctx, int64_t n, const T* in, T* out, doubl
             return ASMC_OK;
         }
     }
+    // (after the flat kernel, which stages nothing: fp64 d = 128 and fp32 d = 256 have no other kernel)
+    ASMC_REQUIRE(lds <= 64 * 1024, "row too long for one LDS tile");
     if (vec == 16 && (p.d == 8 || p.d == 16 || p.d == 32 || p.d == 64 || p.d == 128) && !getenv("ASMC_TRANSFORM_GENERIC")) {
         switch (p.d) {
 #define TR_CASE(DD) \

@@ -30,7 +30,8 @@ __device__ __forceinline__ double floored_mod(double a, double b) {
     return m;
 }
 
-__device__ __forceinline__ double clip(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+// numpy's clip: NaN stays NaN (fmin / fmax would return the bound, and a NaN coordinate would leave as a finite clamp end)
+__device__ __forceinline__ double clip(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One coordinate of the transform chain (shared by both kernels): returns the transformed value, adds the bounded block's
 // element term to lj_b and reports whether the coordinate belongs to that block.
@@ -41,11 +42,15 @@ struct CoordPar {  // the table row of one coordinate, held in registers by the 
 };
 // a / b from the stored reciprocal y = RN(1 / b): q0 = RN(a y), r = a - b q0 (exact in an FMA), q = RN(q0 + r y) - the
 // correctly rounded quotient (Markstein) for three FMAs instead of the ~30-instruction IEEE division sequence, whose
-// v_rcp_f64 made the forward transforms ALU-bound
+// v_rcp_f64 made the forward transforms ALU-bound.  A non-finite q0 (a = +-inf or NaN, or an overflowing quotient) is already
+// what the division returns; the residual of an infinity would be NaN.  Correct rounding holds while y, q0 and the residual are
+// normal numbers - |b| and |a / b| well inside (2^-1022, 2^1022); tests/test_gpu_transforms.py checks 1e-100 .. 1e100 bit for bit -
+// not for a subnormal reciprocal or quotient, and q0 may overflow where a / b is the largest finite number.
 __device__ __forceinline__ double div_by(double a, double b, double y) {
     const double q0 = a * y;
     const double r = fma(-b, q0, a);
-    return fma(r, y, q0);
+    const double q = fma(r, y, q0);
+    return fabs(q0) <= 1.7976931348623157e308 ? q : q0;
 }
 // HINTS: ASMC_TR_NO_* bits known at compile time - the branches they rule out are not even compiled (the forward kernel
 // with fmod, log, log1p and erfinv all inlined twice needed 256 VGPRs: one wave per SIMD)
@@ -82,9 +87,10 @@ __device__ __forceinline__ double transform_coord(double v, const CoordPar& c, b
             double u;
             if (!(HINTS & ASMC_TR_NO_LOGIT) && ((HINTS & ASMC_TR_NO_PROBIT) || kind == 1)) {
                 // sigmoid and log u + log(1 - u) from ONE exponential: with e = exp(-|v|), r = 1 / (1 + e):
-                // u = r (v >= 0) or e r, and log u + log(1 - u) = -|v| - 2 log(1 + e); on the clamped ends the clamp's own
-                // constant.  (The reference's expressions - utils.py:196-245 - cost an exp, a division and two logs; the
-                // values agree to a few ulp.)
+                // u = r (v >= 0) or e r, and log u + log(1 - u) = -|v| - 2 log(1 + e); on a clamped end the reference's own
+                // expression on that end (the two ends differ by 2.9e-11 at eps = 1e-6: fl(1 - eps) is not 1 - eps).  (The
+                // reference's expressions - utils.py:196-245 - cost an exp, a division and two logs; the values agree to a few
+                // ulp.)
                 const double av = fabs(v);
                 const double ex = exp(-av);
                 const double x1 = 1.0 + ex;  // (1, 2]
@@ -94,7 +100,10 @@ __device__ __forceinline__ double transform_coord(double v, const CoordPar& c, b
                 u = v >= 0.0 ? r : ex * r;
                 const bool clamped = u < p.eps || u > 1.0 - p.eps;
                 u = clip(u, p.eps, 1.0 - p.eps);
-                lj_b += clamped ? log(p.eps) + log1p(-p.eps) : -av - 2.0 * bm_log_unit(x1);
+                if (clamped)
+                    lj_b += log(u) + log1p(-u);
+                else
+                    lj_b += -av - 2.0 * bm_log_unit(x1);
             } else {
                 lj_b += -(0.5 * (2.0 * half_log_2pi + v * v));
                 u = 0.5 * (1.0 + erf(v / 1.4142135623730951));

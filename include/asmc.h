@@ -704,7 +704,22 @@ int64_t asmc_pcn_flow_nonfinite(asmc_ctx* ctx);
  * wherever kind != 0 or periodic), mean / std (both NULL: no affine stage).  The two constants are the
  * reference's scalars in FORWARD sign: unit_logj = -sum_{kind != 0} log(upper - lower),
  * affine_logj = -sum log|std| (computed by the host so that they round as the reference's do).
- * In-place operation (z_dev == x_dev) is allowed. */
+ * In-place operation (z_dev == x_dev) is allowed.
+ * Non-finite inputs map as the reference's numpy expressions map them (np.clip and IEEE division propagate NaN;
+ * tests/test_transform_ref.py holds the table, tests/test_gpu_transforms.py checks every kernel against it):
+ *   forward  NaN                                     -> NaN; the row's log|det J| is NaN if the coordinate is bounded
+ *            +-inf, bounded and not periodic          -> the clamp end on the same side (logit / probit of 1 - eps or eps),
+ *                                                        finite log|det J|
+ *            +-inf, periodic                          -> NaN (fmod of an infinity)
+ *            +-inf, neither, with an affine stage     -> +-inf, the sign following std
+ *   inverse  NaN                                     -> NaN (and the row's log|det J|, if the coordinate is bounded)
+ *            +-inf, logit (after the affine stage)    -> the clamped end lower + (upper - lower) * {eps, 1 - eps}, with
+ *                                                        the clamp's term log u + log1p(-u) at that end
+ *            +-inf, probit                            -> upper / lower, log|det J| = -inf
+ * Row length: a row of 16 * 2^k bytes (k <= 6: fp64 d = 2 .. 128, fp32 d = 4 .. 256, powers of two) whose pointers are 16-byte
+ * aligned is served without staging; every other row goes through one LDS tile of 64 rows and may be at most 1008 bytes long -
+ * fp64 d <= 126, fp32 d <= 252.  Longer rows (below ASMC_MAX_DIMS though they are), and power-of-two rows above 1008 bytes at
+ * pointers that are not 16-byte aligned, return ASMC_ERR_ARG ("row too long for one LDS tile") before anything is launched. */
 #define ASMC_TR_NO_PERIODIC 1 /* hints: what the tables do NOT contain (0 = unknown); they let the kernels compile */
 #define ASMC_TR_NO_LOGIT 2    /* the unused branches out (fmod, log / log1p / exp, erf / erfinv) */
 #define ASMC_TR_NO_PROBIT 4
