@@ -44,7 +44,11 @@ __device__ __forceinline__ double mixture_eval(const MixDev& m, int d, const cha
         best = fmax(best, v);
     }
     if (C == 1) return terms[0];
-    if (best == -INFINITY) return -INFINITY;
+    if (best == -INFINITY) {  // every term -inf or NaN (fmax skips a NaN): their sum - -inf, or NaN for a row with a NaN coordinate
+        double t = 0.0;
+        for (int c = 0; c < C; c++) t += terms[c];
+        return t;
+    }
     double s = 0.0;
     for (int c = 0; c < C; c++) s += exp(terms[c] - best);
     return best + log(s);
@@ -260,6 +264,7 @@ __device__ __forceinline__ double mixture_eval_regs(const MixDev& m, const doubl
             s += exp(tc - best);
         }
     }
+    // (a row with a NaN coordinate: the first term is NaN, no comparison above holds and best + log(s) is NaN - DESIGN.md §3.15)
     return best == -INFINITY ? -INFINITY : best + log(s);
 }
 
@@ -1256,7 +1261,7 @@ __global__ __launch_bounds__(ASMC_BLOCK) void k_mixture_flat(int64_t n, int d, i
             for (int k = 0; k < EPT; k++) {
                 xv[k] = (double)vals[k];
                 if (premap) {
-                    xv[k] = fmin(fmax(xv[k] * pa[k] + pb[k], plo[k]), phi[k]);
+                    xv[k] = clip(xv[k] * pa[k] + pb[k], plo[k], phi[k]);  // (NaN stays NaN: fmin / fmax would hand out a clamp end)
                     extra = fma(ph[k] * xv[k], xv[k], extra);
                 }
             }
@@ -1282,8 +1287,11 @@ __global__ __launch_bounds__(ASMC_BLOCK) void k_mixture_flat(int64_t n, int d, i
             }
             double r = terms[0];
             if (C > 1) {
-                if (best == -INFINITY) {
-                    r = -INFINITY;
+                if (best == -INFINITY) {  // every term -inf or NaN: their sum (mixture_eval)
+                    r = 0.0;
+#pragma unroll
+                    for (int c = 0; c < CMAX; c++)
+                        if (c < C) r += terms[c];
                 } else {
                     double ssum = 0.0;
 #pragma unroll
@@ -2149,6 +2157,8 @@ int asmc_ref_factor_launch(asmc_ctx* ctx, int d, const double* sum, const double
     }
     // d <= 32 is bound by the per-column latency whatever the block (38-41 us from 256 to 1024 threads); d = 128 by the trailing
     // updates: 683 us with 256 threads, 516 with 1024
+    // (ASMC_REF_THREADS is a debugging knob for that measurement: a block smaller than d threads is not supported by the kernel -
+    // its last passes give every column a thread - and no test covers the knob)
     static const int ref_env = getenv("ASMC_REF_THREADS") ? atoi(getenv("ASMC_REF_THREADS")) : 0;
     const int ref_threads = ref_env > 0 ? ref_env : (d <= 32 ? REF_THREADS : 1024);
     ASMC_LAUNCH(ctx, st, "k_ref_factor", k_ref_factor, dim3(1), dim3(ref_threads), lds, st, d, sum, gram, n_mean, denom, out,

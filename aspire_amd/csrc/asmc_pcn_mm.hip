@@ -116,7 +116,11 @@ __device__ __forceinline__ double mm_mixture(const MixDev& m, const double* __re
         best = fmax(best, terms[c]);
     }
     if (m.C == 1) return terms[0];
-    if (!(best > -INFINITY)) return best;
+    if (!(best > -INFINITY)) {  // every term -inf or NaN: their sum (mixture_eval)
+        double t = 0.0;
+        for (int c = 0; c < m.C; c++) t += terms[c];
+        return t;
+    }
     double sum = 0.0;
     for (int c = 0; c < m.C; c++) sum += exp(terms[c] - best);
     return best + log(sum);
@@ -452,7 +456,10 @@ __global__ __launch_bounds__(64 * (D / 32)) void k_gram_mm(int64_t n, const T* _
 // coordinate block b, and since the A operand of block row I and the B operand of block column J have the same lane layout the
 // same registers feed all lower blocks (I, J).  Every byte is loaded once and nothing is staged: 103 -> 60 us at 1M x 32 (the LDS
 // version moved 2.4 TB/s), 516 -> 1xx us at 1M x 64.  Same particle-to-block assignment (32-row tiles) and the same accumulation
-// order per accumulator as k_gram_mm<T, D>: the same bits.
+// order per accumulator as k_gram_mm<T, D>: the same bits WHEN BOTH RUN ON THE SAME GRID (tests/test_gpu_moments_density.py compares them
+// bit for bit) - always at d = 32; at d = 64 asmc_gram_mm_launch caps this kernel at eight blocks per CU and the LDS form at two, so
+// above 64 rows per CU (n > 16 384 on 256 CUs) the rows are dealt to other blocks, the block partials are other sums and the last
+// bits differ (each within the same bound of the exact sum).
 template <typename T, int D>
 __global__ __launch_bounds__(64) void k_gram_stream(int64_t n, const T* __restrict__ x, const double* __restrict__ center,
                                                    double n_div, double* __restrict__ partials) {

@@ -397,7 +397,10 @@ int asmc_gather(asmc_ctx* ctx, int64_t n_in, int64_t n_out, const int64_t* idx_d
  * asmc_gaussian_draw: analytic diagonal-Gaussian proposal (a `Flow`-interface object with
  *   sample_and_log_prob, flows/base.py:11-98): x = mu + sigma * xi (Philox4x32-10 normals, keyed
  *   by seed; counter = global particle index gid0+i, draw id), lq = log N(x; mu, diag sigma^2).
- * asmc_mixture_logpdf: evaluate a built-in density over the batch.
+ * asmc_mixture_logpdf: evaluate a built-in density over the batch.  Non-finite rows (every component count, every kernel; the
+ *   same rule in asmc_mixture_logpdf_premap and in the oracle's orc_diag_mixture_logpdf): a row with a NaN coordinate gives NaN;
+ *   a row whose every term logw_c - q_c / 2 is -inf (a +-inf coordinate, a row too far for fp64, components with logw = -inf)
+ *   gives -inf.  (The mutation kernels evaluate the same densities and map a NaN log-target to -inf themselves.)
  * asmc_compact_valid: keep rows with finite lp and ll, preserving order (mcmc.py:88-90);
  *   n_valid_host receives the count; outputs must hold n rows. */
 int asmc_gaussian_draw(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const double* mu_dev,
@@ -411,7 +414,9 @@ int asmc_mixture_logpdf(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void
  * preconditioned coordinate z' when the flow's data transform and the preconditioning transform share their bounded ->
  * unbounded stage (reference flows/torch/flows.py:368-387 behind transforms.py:270-316): the probit / erfinv round trip
  * z' -> x' -> flow latent collapses to an affine map, the clamp reproducing the forward transform's eps clip.
- * Rows must be a power-of-two number (<= 64) of 16-byte pieces, <= 4 components. */
+ * Rows must be a power-of-two number (<= 64) of 16-byte pieces, 16-byte aligned, <= 4 components (anything else:
+ * ASMC_ERR_UNSUPPORTED).  The clamp is numpy's clip: a NaN coordinate passes through it and the row gives NaN, never the
+ * density at a clamp end. */
 int asmc_mixture_logpdf_premap(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x_dev, const double* premap_dev,
                                const asmc_mixture* density, double* out_dev, asmc_stream stream);
 /* asmc_compact_valid: *n_valid_host == n means the population was already compact and NOTHING was copied - the caller keeps
