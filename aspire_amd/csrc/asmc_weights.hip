@@ -573,8 +573,13 @@ __device__ __forceinline__ void bis_shard_decide(BisLds& L, const double* __rest
 //     exp(lw_i(beta_j) - m_j) = exp(lw_i(beta_1) - m_1) * r_i^(j-1),   r_i = exp(h (Delta_i - Delta_max)) <= 1:
 // two exponentials per particle instead of sixteen.  The first factor uses the reference's own expression for the
 // log-weight (samples.py:1222-1224); the progression is non-increasing in j, so it can neither overflow nor lose
-// a term that matters.  Relative deviation from direct exponentials: ~1e-14 (it decides `eff >= target`
-// comparisons only; the values reported at the chosen beta carry the same 1e-14).
+// a term that matters.  Deviation from the long-double sums of the exact log-weights at the node's float, per term and
+// relative (u = 2^-53; DESIGN.md section 3.16, tests/weights_ref.py): u (8 t (|lq| + |ll + lp|) + |lw| + 4 |lw - m|) + 6 u |m|
+// + (LU + 1) u (|Delta - Delta_max| + |Delta_max|) + (15 + L) u + 2 E, t = beta - beta0, LU the depth of the dyadic grid, L the
+// addition chain, E = 3.4 u the bound on exp.  That is 1e-14 .. 1e-13 for |Delta|, |lq| of order 10 .. 100 and grows in
+// proportion: 1e-10 at |Delta| = 3e4, 1e-9 with a common offset of 1e6 in ll and lq (where the reference's own fp64 expression
+// has lost as much).  Measured: below 0.3 of that bound on every population of tests/test_gpu_weights.py.  It decides
+// `eff >= target` comparisons; the values reported at the chosen beta carry the same bound.
 // The block that arrives last (ticket counter behind an agent-scope release) reduces the partials and runs the
 // tail, so a round costs one launch; the first round derives its grid from m(1) (max kernel) itself.
 #define BIS_THREADS 512  // one block per CU: few, large partial records keep the last block's reduction short
@@ -603,11 +608,16 @@ __global__ __launch_bounds__(BIS_THREADS) void k_bis_sums(int64_t n, const doubl
         __syncthreads();  // (s_S, s_eff are reused by the last block below)
     } else if (round == 0) {
         m_one = key_to_f64(keys[0]);
+        // sharded search: a rank without a finite log-weight (local m(1) = -inf) reduces against 0, as a block of k_is_weights
+        // does - its sums are then zero, not exp(-inf + inf) = NaN, and the merge of the rank records (k_bis_decide,
+        // bis_shard_decide) gives them the factor exp(-inf) = 0 against the other ranks' maximum.  The record still reports
+        // -inf.  The single-rank search keeps the reference's NaN for a population without any finite log-weight.
+        const double m_loc = (rec_out && m_one == -INFINITY) ? 0.0 : m_one;
         const double lo = init.beta0;
         double b1 = 1.0;
         for (int lev = 0; lev < BIS_LEVELS; lev++) b1 = 0.5 * (b1 + lo);  // leftmost leaf of the first tree
         const double inv = 1.0 / (1.0 - lo);
-        c1 = lo - b1, c2 = b1 - lo, m1 = m_one * ((b1 - lo) * inv), h = (1.0 - lo) / 16.0, dmax = m_one * inv;
+        c1 = lo - b1, c2 = b1 - lo, m1 = m_loc * ((b1 - lo) * inv), h = (1.0 - lo) / 16.0, dmax = m_loc * inv;
     } else {
         if (st[2] != 0.0) return;  // converged in an earlier round (uniform across the grid)
         c1 = st[34], c2 = st[35], m1 = st[36], h = st[37], dmax = st[38];
@@ -1455,6 +1465,18 @@ int asmc_importance_result(asmc_ctx* ctx, double* out_host, asmc_stream stream) 
 }
 
 int asmc_importance_available(asmc_ctx* ctx) { return ctx && !ctx->isw_disabled ? 1 : 0; }
+
+// The scan-tile sums the last asmc_importance_step's weight kernel left in the context's scratch (one per ASMC_SCAN_TILE
+// particles; the exact scan behind it reads them as hints and leaves them alone while there are at most 1024 tiles), copied
+// to out_dev[ceil(n / ASMC_SCAN_TILE)] on the stream: a read-back for tests and diagnostics.
+int asmc_importance_tile_sums(asmc_ctx* ctx, int64_t n, double* out_dev, asmc_stream stream) {
+    ASMC_REQUIRE(ctx && out_dev, "null pointer");
+    ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
+    const int64_t n_tiles = (n + ASMC_SCAN_TILE - 1) / ASMC_SCAN_TILE;
+    ASMC_REQUIRE(n_tiles <= 1024, "above 1024 tiles the scan overwrites the tile sums with their prefix");
+    ASMC_HIP(hipMemcpyAsync(out_dev, ctx->d_tiles, sizeof(double) * (size_t)n_tiles, hipMemcpyDeviceToDevice, as_stream(stream)));
+    return ASMC_OK;
+}
 
 static inline void bis_state(asmc_ctx* ctx, double** d_st, unsigned int** d_ticket) {
     *d_st = ctx->d_small + 2560;

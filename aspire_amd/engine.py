@@ -308,6 +308,12 @@ class HipEngine:
         return (float(out[0]), float(out[4]), bool(out[2]), int(out[3]), int(out[5]), trip, tuple(map(float, out[10:13])),
                 float(out[13]), float(out[14]), bool(out[15]))
 
+    def importance_tile_sums(self, n: int) -> torch.Tensor:
+        """The weights' sums per 2048-particle scan tile of the last `importance_step` over n particles (a read-back for tests)."""
+        out = self.empty((n + 2047) // 2048)
+        check(self.lib.asmc_importance_tile_sums(self._ctx, n, _dptr(out), self._stream), "asmc_importance_tile_sums")
+        return out
+
     # sharded search (smc_math.find_beta_sharded drives the rounds; the all-gather between the halves is the caller's)
     def find_beta_shard_reduce(self, ll, lp, lq, beta0: float, rnd: int, rec: torch.Tensor):
         self._chk3(ll, lp, lq)

@@ -179,6 +179,10 @@ int asmc_importance_result_enqueue(asmc_ctx* ctx, asmc_stream stream);
  * (not fully resident, e.g. another process's kernel of the same kind on the GPU): that step reported found = 0, the counters
  * were reset, and the caller stays on the step-by-step entry points. */
 int asmc_importance_available(asmc_ctx* ctx);
+/* Copies the weights' sums per 2048-particle scan tile that the last asmc_importance_step left in the context's scratch to
+ * out_dev[ceil(n / 2048)] (n: that step's; at most 1024 tiles, above that the scan has replaced them by their prefix).  A
+ * read-back for tests and diagnostics; no synchronisation. */
+int asmc_importance_tile_sums(asmc_ctx* ctx, int64_t n, double* out_dev, asmc_stream stream);
 /* The same search with the particles sharded over `world` ranks (one process per GPU; the reference has no
  * distributed mode).  A round is split at the rank boundary and never synchronises with the host:
  *   asmc_find_beta_shard_reduce  this rank's sums of the round's 16 candidates -> rec_dev[ASMC_BIS_REC]
@@ -189,7 +193,8 @@ int asmc_importance_available(asmc_ctx* ctx);
  * Rounds 0, 1, 2, ... until asmc_find_beta_shard_result (the only synchronising call; same out_host[13] as
  * asmc_find_beta, N = n_global) reports convergence; rounds after convergence are no-ops.  In round 0 the ranks
  * shift by their local maximum at beta = 1 and the decide step rescales to the global one, so no separate
- * all-reduce(max) is needed. */
+ * all-reduce(max) is needed.  A rank without a finite log-weight (every row of zero likelihood) contributes zero sums
+ * and the shift base -inf, which the merged maximum ignores: the search is the global population's. */
 int asmc_find_beta_shard_reduce(asmc_ctx* ctx, int64_t n_local, const double* ll_dev, const double* lp_dev,
                                 const double* lq_dev, double beta0, int round, double* rec_dev, asmc_stream stream);
 int asmc_find_beta_shard_decide(asmc_ctx* ctx, const double* recs_dev, int world, int64_t n_global, double beta0,
