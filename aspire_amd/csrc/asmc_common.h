@@ -18,6 +18,7 @@
 #define BM_SC_N 256                   // [0, 256): (sin, cos)(2 pi (k + 1/2) / 256)
 #define BM_LG_N 128                   // [256, 384): (rc_i, 2 ln rc_i)
 #define BM_TAB_N (BM_SC_N + BM_LG_N)
+#define ASMC_FUSED_IMAGE_BYTES (160 * 1024)  // the fused flow-proposal step's LDS image: at most a CU's whole LDS
 
 void asmc_set_error(const char* fmt, ...);
 void asmc_bm_table_host(double* tab);  // asmc_ctx.hip: the 2 * BM_TAB_N doubles (long double libm)
@@ -129,6 +130,7 @@ struct asmc_ctx {
     unsigned long long ptab_tag, ysplit_seq;  // who packed d_ptab last (0 = anyone; else the split session's number)
     double* d_ptab;                // [2*32*32 + 32 + 3*8*(1+2*32)] packed pCN parameter block (d <= 32)
     double* d_bmtab;               // [2 * 384] Box-Muller tables of the default noise (asmc_pcn_dev.h bm_pair32)
+    void* d_fimg;                  // [ASMC_FUSED_IMAGE_BYTES] LDS image of the fused flow-proposal step (asmc_pcn_fused.hip): built once per mutation call, copied by every step
     double* d_mmtab;               // [2 * 144 * 64] MFMA operand images of L and Linv (d = 64 / 128; NULL when d_max < 64)
     double* d_f16tab;              // resident tables of the flow-proposal step at d = 64 / 128 (asmc_flow16.hip; allocated on first use)
     size_t f16tab_bytes;

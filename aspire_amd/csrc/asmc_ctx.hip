@@ -219,6 +219,7 @@ int asmc_ctx_create(asmc_ctx** ctx_out, int device, int64_t n_max, int d_max) {
     dmalloc((void**)&c->d_select, sizeof(long long) * (2 * (ASMC_SELECT_THREADS / 64) + 8));
     dmalloc((void**)&c->d_ptab, sizeof(double) * (2 * 32 * 32 + 32 + 3 * ASMC_MAX_COMPONENTS * (1 + 2 * 32) + 64));
     dmalloc((void**)&c->d_bmtab, sizeof(double) * 2 * BM_TAB_N);
+    dmalloc((void**)&c->d_fimg, ASMC_FUSED_IMAGE_BYTES);
     dmalloc((void**)&c->d_ref, sizeof(double) * (128 + 128 * 128));
     if (e == hipSuccess) {
         double tab[2 * BM_TAB_N];
@@ -264,6 +265,7 @@ int asmc_ctx_destroy(asmc_ctx* c) {
     (void)hipFree(c->d_select);
     (void)hipFree(c->d_ptab);
     (void)hipFree(c->d_bmtab);
+    (void)hipFree(c->d_fimg);
     (void)hipFree(c->d_ref);
     if (c->prof_ev) {
         for (int i = 0; i < 2 * ASMC_PROF_MAX; i++) (void)hipEventDestroy(c->prof_ev[i]);

@@ -741,25 +741,41 @@ __device__ __forceinline__ void coupling_layer_hs1p(const float (&cond)[H / 2], 
 }
 
 // Stage `n_layers` coupling layers from the fp32 pack in HBM into LDS as split-fp16 operand images (biases copied).
+// Eight rows of the block at a time: all of a thread's loads of a batch (a bias word, or the two halves of a weight pair) are
+// issued before its first conversion, so a batch costs one round trip to memory, not eight.  Each word goes through the same
+// conversion as before, so the image is the same.
 template <int H, int W, int THREADS>
 __device__ __forceinline__ void flow_stage_hs(float* __restrict__ sp, const float* __restrict__ packed, int n_layers) {
     using FD = FlowDims<H, W>;
-    constexpr int L4 = FD::LAYER / 4, B4 = FD::BIAS / 4;
+    constexpr int L4 = FD::LAYER / 4, B4 = FD::BIAS / 4, BATCH = 8;
     const int total4 = n_layers * L4;
-    for (int i4 = threadIdx.x; i4 < total4; i4 += THREADS) {
-        const int in_layer = i4 % L4;
-        if (in_layer < B4) {
-            reinterpret_cast<float4*>(sp)[i4] = reinterpret_cast<const float4*>(packed)[i4];
-            continue;
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(packed);
+    for (int base = threadIdx.x; base < total4; base += THREADS * BATCH) {
+        float4 f0[BATCH], f1[BATCH];
+#pragma unroll
+        for (int q = 0; q < BATCH; q++) {
+            const int i4 = base + q * THREADS, in_layer = i4 % L4;
+            const bool in = i4 < total4, bias = in_layer < B4;
+            const bool pair = in && !bias && !(((in_layer - B4) / 64) & 1);  // the even slot group's thread converts the pair
+            f0[q] = f1[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((in && bias) || pair) f0[q] = g4[i4];
+            if (pair) f1[q] = g4[i4 + 64];
         }
-        const int local = in_layer - B4;
-        if ((local / 64) & 1) continue;  // the even slot group's thread converts the pair
-        const float4 f0 = reinterpret_cast<const float4*>(packed)[i4], f1 = reinterpret_cast<const float4*>(packed)[i4 + 64];
-        const float xv[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-        half8 hi, lo;
-        float wmax = 0.0f;  // (weights beyond the fp16 range are refused when the flow is packed: asmc_coupling_pack)
-        split8_f16<false>(xv, hi, lo, wmax);
-        reinterpret_cast<half8*>(sp)[i4] = hi;
-        reinterpret_cast<half8*>(sp)[i4 + 64] = lo;
+#pragma unroll
+        for (int q = 0; q < BATCH; q++) {
+            const int i4 = base + q * THREADS, in_layer = i4 % L4;
+            if (i4 >= total4) continue;
+            if (in_layer < B4) {
+                reinterpret_cast<float4*>(sp)[i4] = f0[q];
+                continue;
+            }
+            if (((in_layer - B4) / 64) & 1) continue;
+            const float xv[8] = {f0[q].x, f0[q].y, f0[q].z, f0[q].w, f1[q].x, f1[q].y, f1[q].z, f1[q].w};
+            half8 hi, lo;
+            float wmax = 0.0f;  // (weights beyond the fp16 range are refused when the flow is packed: asmc_coupling_pack)
+            split8_f16<false>(xv, hi, lo, wmax);
+            reinterpret_cast<half8*>(sp)[i4] = hi;
+            reinterpret_cast<half8*>(sp)[i4 + 64] = lo;
+        }
     }
 }

@@ -3234,6 +3234,11 @@ static int pcn_mutate_flow_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, d
             ASMC_HIP(hipMemsetAsync(ctx->d_tilectr, 0, ASMC_TILECTR_BYTES + ((size_t)((n + 63) / 64) + 15) / 16 * 16, st));
             pd.tile_par = ctx->d_flags;
         }
+        int img_words = 0;  // the steps' LDS image, built once per call (0: every step stages for itself)
+        if (fused) {
+            rc = asmc_pcn_flow_fused_stage(ctx, pd, flow, &img_words, st);
+            if (rc) return rc;
+        }
         for (int t = 0; t < (fused ? n_steps : 0); t++) {
             const uint32_t step = step0 + (uint32_t)t;
             rc = pcn_prepare_gamma(ctx, n, pd, step, st);
@@ -3251,7 +3256,7 @@ static int pcn_mutate_flow_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, d
                 return ASMC_ERR_ARG;
             }
             rc = asmc_pcn_flow_fused_launch(ctx, n, prm->x_dtype == ASMC_F64 ? ASMC_F64 : ASMC_F32, ll, lp, lq, pd, flow, d_rho, step,
-                                            ctx->d_tilectr + t, d_block, &grid, ad, st);
+                                            ctx->d_tilectr + t, d_block, &grid, ad, img_words, st);
             if (rc) return rc;
             // the kernel's last block left this rank's count in the step's cell: exchange it - lagged runs at the end of a block
             if (ctx->count_hook && ((t + 1) % lag == 0 || t == n_steps - 1)) {

@@ -71,6 +71,7 @@ __device__ __forceinline__ void mv_for_each(F& f) {
 #define FUSED_MVMFMA FUSED_INPLACE
 #endif
 typedef double fused_d4 __attribute__((ext_vector_type(4)));
+typedef unsigned fused_u4 __attribute__((ext_vector_type(4)));  // one 16-byte word of the LDS image
 __device__ __forceinline__ void fused_swap32(double& x, double& y) {  // x.lanes[32..63] <-> y.lanes[0..31]
     const unsigned long long xb = __builtin_bit_cast(unsigned long long, x), yb = __builtin_bit_cast(unsigned long long, y);
     const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)xb, (unsigned)yb, false, false);
@@ -103,24 +104,28 @@ __device__ __forceinline__ void fused_transpose4(double& q0, double& q1, double&
 #ifndef MV_CHUNK
 #define MV_CHUNK 8  // columns of L between two ordering points of the mat-vec
 #endif
-// KIND: ASMC_FLOW_COUPLING - the coupling layers described above; ASMC_FLOW_MAF - masked autoregressive transforms
-// (flows/torch/flows.py:140-168, the reference's default flow class): a transform is a coupling layer whose conditioner input and
-// transformed block are both the whole x (asmc_flow.hip), so a flow tile holds 16 coordinates per lane instead of 8 + 8 and the
-// swap pairs coordinate i with coordinate 16 + i.
-// MIX: built-in MIXTURE targets (2 .. FUSED_MAX_COMPONENTS components) - their own instantiations: the component loop keeps the
-// mat-vec accumulators alive past the first quadratic forms, and compiled into the single-Gaussian kernel it cost the headline
-// 90 spilled registers (0.294 -> 0.320 ms per step).
-template <typename T, int W, int NOISE, bool HS, int KIND = ASMC_FLOW_COUPLING, bool MIX = false>
-__global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
-    int64_t n, double* __restrict__ ll, double* __restrict__ lp, double* __restrict__ lq, const double* __restrict__ ptab,
-    PcnScalars p, const double* rho_ptr, uint32_t step, const float* __restrict__ packed, int n_layers,
-    const float* __restrict__ loc, const float* __restrict__ scale, float ladj0, float base_const,
-    unsigned int* __restrict__ tile_counter, long long* __restrict__ block_counts, PcnAdaptArgs ad, int par_words, int affine) {
-    constexpr int D = 32, H = 16, THREADS = FUSED_THREADS;
-    constexpr int HF = KIND == ASMC_FLOW_MAF ? 32 : H;  // H of the flow's layer templates (lane halves hold HF / 2 inputs)
-    static_assert(KIND == ASMC_FLOW_COUPLING || HS, "the autoregressive variant runs the split-fp16 layers only");
+// layout of the pCN tables in LDS, in doubles from their start (behind the flow's weights)
+constexpr int FUSED_D = 32;
+constexpr int T_MU = FUSED_D * FUSED_D, T_LLMU = T_MU + FUSED_D, T_LLPR = T_LLMU + FUSED_D, T_LPMU = T_LLPR + FUSED_D, T_LPPR = T_LPMU + FUSED_D,
+              T_LOGW = T_LPPR + FUSED_D, T_LOC = T_LOGW + 2;  // then loc / scale / 1/scale: 3 x FUSED_D floats = 1.5 FUSED_D doubles
+static_assert(T_LOC + 3 * FUSED_D / 2 <= FUSED_TL_DOUBLES, "pCN tables");
+// matrix-core variant: operand image of L | mu | per target t (0 = likelihood, 1 = prior) and component c: mean, precision |
+// log-weights [t * 4 + c] | loc / scale / 1/scale (floats); per-row tables in the lanes' reading order (below)
+constexpr int M_MU = 12 * 64, M_MIX = M_MU + FUSED_D, M_LOGW = M_MIX + 2 * FUSED_MAX_COMPONENTS * 2 * FUSED_D, M_LOC = M_LOGW + 2 * FUSED_MAX_COMPONENTS;
+static_assert(M_LOC + 3 * FUSED_D / 2 <= FUSED_TL_DOUBLES, "pCN tables (matrix-core variant)");
+constexpr bool MVM = FUSED_MVMFMA && FUSED_INPLACE;  // the mat-vec on the fp64 matrix cores
+
+// What a step launch holds in LDS and no launch of one mutation call changes: the flow's weights as the layers read them (split-fp16
+// operand images, or the fp32 pack), the pCN tables behind them, the Box-Muller tables of the default noise behind those.  The
+// weights are fixed for the call, mu / L / the targets / loc / scale change once per temperature - so the image is built ONCE per
+// call by k_fused_stage_image (this function into its own LDS, then a straight dump) and a step launch copies it in one sweep of
+// loads; a step launched without an image runs this function itself (ASMC_FUSED_STAGE=inline): the same code, the same bytes.
+template <int W, int NOISE, bool HS, int KIND>
+__device__ __forceinline__ void fused_stage_tables(float* __restrict__ sp, const double* __restrict__ ptab, const PcnScalars& p,
+                                                   const float* __restrict__ packed, int n_layers, const float* __restrict__ loc,
+                                                   const float* __restrict__ scale) {
+    constexpr int D = FUSED_D, THREADS = FUSED_THREADS, HF = KIND == ASMC_FLOW_MAF ? 32 : 16;
     using FD = FlowDims<HF, W>;
-    extern __shared__ __align__(16) float sp[];
     if (HS) {
         flow_stage_hs<HF, W, THREADS>(sp, packed, n_layers);  // split-fp16 operand images (asmc_flow_dev.h)
     } else {  // flow weights -> LDS; all of a thread's loads are issued before its first LDS store
@@ -144,14 +149,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
     // precision rows and constants, the flow's loc / scale.  (Scalar loads would be the natural home of wave-uniform
     // coefficients, but inside this kernel's tile loop LLVM issues all ~1400 of them up front and spills the SGPRs.)
     double* tl = reinterpret_cast<double*>(sp + (size_t)n_layers * FD::LAYER);
-    constexpr int T_MU = D * D, T_LLMU = T_MU + D, T_LLPR = T_LLMU + D, T_LPMU = T_LLPR + D, T_LPPR = T_LPMU + D,
-                  T_LOGW = T_LPPR + D, T_LOC = T_LOGW + 2;  // then loc / scale / 1/scale: 3 x D floats = 1.5 D doubles
-    static_assert(T_LOC + 3 * D / 2 <= FUSED_TL_DOUBLES, "pCN tables");
-    // matrix-core variant: operand image of L | mu | per target t (0 = likelihood, 1 = prior) and component c: mean, precision |
-    // log-weights [t * 4 + c] | loc / scale / 1/scale (floats); per-row tables in the lanes' reading order (below)
-    constexpr int M_MU = 12 * 64, M_MIX = M_MU + D, M_LOGW = M_MIX + 2 * FUSED_MAX_COMPONENTS * 2 * D, M_LOC = M_LOGW + 2 * FUSED_MAX_COMPONENTS;
-    static_assert(M_LOC + 3 * D / 2 <= FUSED_TL_DOUBLES, "pCN tables (matrix-core variant)");
-    constexpr bool MVM = FUSED_MVMFMA && FUSED_INPLACE;  // the mat-vec on the fp64 matrix cores
     {
         const double* m0g = ptab + 2 * PTAB_TRI(D) + D;
         // A problem of fewer than 32 dimensions arrives zero-padded to 32 (asmc_pcn_mutate_flow: tables with the identity beyond
@@ -214,8 +211,63 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
         if (!MVM && threadIdx.x == 0) tl[T_LOGW] = m0g[0], tl[T_LOGW + 1] = m0g[PTAB_MIX(D)];
     }
     // ... and the Box-Muller tables of the default noise behind them (6 KB)
+    if (NOISE == ASMC_NOISE_F64) bm_tab_stage<THREADS>(reinterpret_cast<bm_d2*>(tl + FUSED_TL_DOUBLES), p.bmtab);
+}
+// 16-byte words of that image
+template <int W, int NOISE, int KIND>
+__host__ __device__ constexpr int fused_image_words(int n_layers) {
+    return (int)(((size_t)n_layers * FlowDims<(KIND == ASMC_FLOW_MAF ? 32 : 16), W>::LAYER * sizeof(float) + FUSED_TL_DOUBLES * sizeof(double) +
+                  (NOISE == ASMC_NOISE_F64 ? BM_TAB_N * sizeof(bm_d2) : 0)) / 16);
+}
+// one block: stage, then LDS -> img (words the staging leaves unwritten travel as they are: no step reads them)
+template <int W, int NOISE, bool HS, int KIND>
+__global__ __launch_bounds__(FUSED_THREADS) void k_fused_stage_image(const double* __restrict__ ptab, PcnScalars p, const float* __restrict__ packed,
+                                                                     int n_layers, const float* __restrict__ loc, const float* __restrict__ scale,
+                                                                     fused_u4* __restrict__ img, int img_words) {
+    extern __shared__ __align__(16) float sp[];
+    fused_stage_tables<W, NOISE, HS, KIND>(sp, ptab, p, packed, n_layers, loc, scale);
+    __syncthreads();
+    for (int i = threadIdx.x; i < img_words; i += FUSED_THREADS) img[i] = reinterpret_cast<const fused_u4*>(sp)[i];
+}
+
+// KIND: ASMC_FLOW_COUPLING - the coupling layers described above; ASMC_FLOW_MAF - masked autoregressive transforms
+// (flows/torch/flows.py:140-168, the reference's default flow class): a transform is a coupling layer whose conditioner input and
+// transformed block are both the whole x (asmc_flow.hip), so a flow tile holds 16 coordinates per lane instead of 8 + 8 and the
+// swap pairs coordinate i with coordinate 16 + i.
+// MIX: built-in MIXTURE targets (2 .. FUSED_MAX_COMPONENTS components) - their own instantiations: the component loop keeps the
+// mat-vec accumulators alive past the first quadratic forms, and compiled into the single-Gaussian kernel it cost the headline
+// 90 spilled registers (0.294 -> 0.320 ms per step).
+// img / img_words: the call's LDS image (fused_stage_tables) and its size in 16-byte words; img == nullptr: staged here
+template <typename T, int W, int NOISE, bool HS, int KIND = ASMC_FLOW_COUPLING, bool MIX = false>
+__global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
+    int64_t n, double* __restrict__ ll, double* __restrict__ lp, double* __restrict__ lq, const double* __restrict__ ptab,
+    PcnScalars p, const double* rho_ptr, uint32_t step, const float* __restrict__ packed, int n_layers,
+    const float* __restrict__ loc, const float* __restrict__ scale, float ladj0, float base_const,
+    unsigned int* __restrict__ tile_counter, long long* __restrict__ block_counts, PcnAdaptArgs ad, int par_words, int affine,
+    const fused_u4* __restrict__ img, int img_words) {
+    constexpr int D = FUSED_D, H = 16, THREADS = FUSED_THREADS;
+    constexpr int HF = KIND == ASMC_FLOW_MAF ? 32 : H;  // H of the flow's layer templates (lane halves hold HF / 2 inputs)
+    static_assert(KIND == ASMC_FLOW_COUPLING || HS, "the autoregressive variant runs the split-fp16 layers only");
+    using FD = FlowDims<HF, W>;
+    extern __shared__ __align__(16) float sp[];
+    // The image arrives in ONE sweep: every thread issues all of its 16-byte loads (IMG_Q: a CU's whole LDS over the block), then
+    // the words land in LDS, each load waited for in its turn - one round trip to memory where the staging code makes one per
+    // trip of each of its loops, and no conversion, no division, no index arithmetic in front of the first tile.  (The parity
+    // snapshot of the two-halves build below changes from launch to launch and stays here.  Issuing the first tile's state loads
+    // in front of the landing as well was tried: in either order the tile loop then spilled 36 - 40 bytes of registers, so it is not done.)
+    constexpr int IMG_Q = ASMC_FUSED_IMAGE_BYTES / 16 / THREADS;
+    fused_u4 iw[IMG_Q];
+    if (img != nullptr) {
+#pragma unroll
+        for (int q = 0; q < IMG_Q; q++) {
+            const int i4 = q * THREADS + (int)threadIdx.x;
+            iw[q] = img[i4 < img_words ? i4 : img_words - 1];  // (rows beyond the image re-read its last word and store nothing)
+        }
+    } else {
+        fused_stage_tables<W, NOISE, HS, KIND>(sp, ptab, p, packed, n_layers, loc, scale);
+    }
+    double* tl = reinterpret_cast<double*>(sp + (size_t)n_layers * FD::LAYER);
     bm_d2* bmt = reinterpret_cast<bm_d2*>(tl + FUSED_TL_DOUBLES);
-    if (NOISE == ASMC_NOISE_F64) bm_tab_stage<THREADS>(bmt, p.bmtab);
     // ... and the tiles' parity bits (below), one bit per tile, when they fit (par_words > 0): a snapshot is all a launch
     // needs - a tile is read once per launch, before its own wave may flip it
     unsigned* const par_bits = reinterpret_cast<unsigned*>(bmt + BM_TAB_N);
@@ -229,6 +281,14 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
             bits |= nib << (4 * k);
         }
         par_bits[wd] = bits;
+    }
+    if (img != nullptr) {
+        __builtin_amdgcn_sched_barrier(0);  // (every load above is issued before the first wait)
+#pragma unroll
+        for (int q = 0; q < IMG_Q; q++) {
+            const int i4 = q * THREADS + (int)threadIdx.x;
+            if (i4 < img_words) reinterpret_cast<fused_u4*>(sp)[i4] = iw[q];
+        }
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hh = lane >> 5;
@@ -992,10 +1052,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
     }
 }
 
-template <typename T>
-static int launch_pcn_flow_fused(asmc_ctx* ctx, int64_t n, double* ll, double* lp, double* lq, const PcnDev& pd,
-                                 const asmc_coupling* f, const double* rho_ptr, uint32_t step, unsigned int* tile_counter,
-                                 long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, hipStream_t st) {
+// the scalars a step launch and the image builder read
+static PcnScalars fused_scalars(const PcnDev& pd) {
     PcnScalars ps;
     ps.beta = pd.beta;
     ps.nu = pd.nu;
@@ -1011,6 +1069,15 @@ static int launch_pcn_flow_fused(asmc_ctx* ctx, int64_t n, double* ll, double* l
     ps.c_lq = 0;
     ps.bmtab = pd.bmtab;
     ps.tile_par = pd.tile_par;
+    return ps;
+}
+
+template <typename T>
+static int launch_pcn_flow_fused(asmc_ctx* ctx, int64_t n, double* ll, double* lp, double* lq, const PcnDev& pd,
+                                 const asmc_coupling* f, const double* rho_ptr, uint32_t step, unsigned int* tile_counter,
+                                 long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, int img_words, hipStream_t st) {
+    const PcnScalars ps = fused_scalars(pd);
+    const fused_u4* img = img_words > 0 ? reinterpret_cast<const fused_u4*>(ctx->d_fimg) : nullptr;
     const float ladj0 = (float)(-f->log_scale_sum);
     const float base_const = (float)(-0.5 * f->dims * 1.8378770664093453);
     const int64_t n_tiles = (n + 63) / 64;
@@ -1038,7 +1105,7 @@ static int launch_pcn_flow_fused(asmc_ctx* ctx, int64_t n, double* ll, double* l
         }                                                                                                                \
         ASMC_LAUNCH(ctx, st, "k_pcn_flow_fused", kern, dim3(grid), dim3(FUSED_THREADS), lds, st, n, ll, lp, lq,                     \
                     (const double*)ctx->d_ptab, ps, rho_ptr, step, f->packed_dev, (int)f->n_layers, f->loc_dev, f->scale_dev, \
-                    ladj0, base_const, tile_counter, block_counts, adapt, par_words, KD == ASMC_FLOW_MAF ? (int)f->affine : 0);  \
+                    ladj0, base_const, tile_counter, block_counts, adapt, par_words, KD == ASMC_FLOW_MAF ? (int)f->affine : 0, img, img_words);  \
         ASMC_LAUNCH_CHECK();                                                                                             \
         return ASMC_OK;                                                                                                  \
     }
@@ -1095,10 +1162,60 @@ bool asmc_pcn_flow_fused_ok(const asmc_pcn_params* prm, const asmc_coupling* f) 
 }
 
 
+// Builds the LDS image of this mutation call's steps in ctx->d_fimg, on the call's stream: behind the table pack (ctx->d_ptab), in
+// front of the first step.  Rebuilt by every call - flows are re-fitted between calls and mu / L / the targets move with the
+// temperature.  *words_out: the image's 16-byte words, what asmc_pcn_flow_fused_launch takes; 0 with ASMC_FUSED_STAGE=inline (read
+// per call: every step stages for itself, as one process comparing the two paths wants it).
+int asmc_pcn_flow_fused_stage(asmc_ctx* ctx, const PcnDev& pd, const asmc_coupling* f, int* words_out, hipStream_t st) {
+    *words_out = 0;
+    const char* mode = getenv("ASMC_FUSED_STAGE");
+    if (mode && !strcmp(mode, "inline")) return ASMC_OK;
+    const PcnScalars ps = fused_scalars(pd);
+    const bool hs = asmc_flow_math_split();
+#define ASMC_STAGE_CASE(WW, NZ, HSV, KD)                                                                                 \
+    if (f->hidden == WW && pd.noise == NZ && hs == HSV && f->kind == KD) {                                               \
+        auto kern = k_fused_stage_image<WW, NZ, HSV, KD>;                                                                \
+        const int words = fused_image_words<WW, NZ, KD>((int)f->n_layers);                                               \
+        const size_t lds = (size_t)words * 16;                                                                           \
+        if (lds > ASMC_FUSED_IMAGE_BYTES) {                                                                              \
+            asmc_set_error("fused flow step: LDS image of %zu bytes", lds);                                              \
+            return ASMC_ERR_UNSUPPORTED;                                                                                 \
+        }                                                                                                                \
+        static size_t attr_lds_dev[ASMC_MAX_DEVICES] = {0}; size_t& attr_lds = attr_lds_dev[asmc_dev_slot(ctx)];         \
+        if (lds > 64 * 1024 && lds > attr_lds) {                                                                         \
+            ASMC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            attr_lds = lds;                                                                                              \
+        }                                                                                                                \
+        ASMC_LAUNCH(ctx, st, "k_fused_stage_image", kern, dim3(1), dim3(FUSED_THREADS), lds, st, (const double*)ctx->d_ptab, ps, \
+                    f->packed_dev, (int)f->n_layers, f->loc_dev, f->scale_dev, reinterpret_cast<fused_u4*>(ctx->d_fimg), words); \
+        ASMC_LAUNCH_CHECK();                                                                                             \
+        *words_out = words;                                                                                              \
+        return ASMC_OK;                                                                                                  \
+    }
+#define ASMC_STAGE_CASES(WW)                                   \
+    ASMC_STAGE_CASE(WW, ASMC_NOISE_F64, true, ASMC_FLOW_COUPLING)  \
+    ASMC_STAGE_CASE(WW, ASMC_NOISE_F32, true, ASMC_FLOW_COUPLING)  \
+    ASMC_STAGE_CASE(WW, ASMC_NOISE_F64, false, ASMC_FLOW_COUPLING) \
+    ASMC_STAGE_CASE(WW, ASMC_NOISE_F32, false, ASMC_FLOW_COUPLING)
+    ASMC_STAGE_CASES(64)
+#ifndef FUSED_ONLY_HEADLINE
+    ASMC_STAGE_CASES(32)
+    ASMC_STAGE_CASES(128)
+    ASMC_STAGE_CASE(64, ASMC_NOISE_F64, true, ASMC_FLOW_MAF)
+    ASMC_STAGE_CASE(64, ASMC_NOISE_F32, true, ASMC_FLOW_MAF)
+    ASMC_STAGE_CASE(32, ASMC_NOISE_F64, true, ASMC_FLOW_MAF)
+    ASMC_STAGE_CASE(32, ASMC_NOISE_F32, true, ASMC_FLOW_MAF)
+#endif
+#undef ASMC_STAGE_CASES
+#undef ASMC_STAGE_CASE
+    asmc_set_error("fused flow step: unsupported flow (kind %d, hidden width %d)", (int)f->kind, (int)f->hidden);
+    return ASMC_ERR_UNSUPPORTED;
+}
+
 int asmc_pcn_flow_fused_launch(asmc_ctx* ctx, int64_t n, int x_dtype, double* ll, double* lp, double* lq, const PcnDev& pd,
                                const asmc_coupling* f, const double* rho_ptr, uint32_t step, unsigned int* tile_counter,
-                               long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, hipStream_t st) {
+                               long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, int img_words, hipStream_t st) {
     if (x_dtype == ASMC_F64)
-        return launch_pcn_flow_fused<double>(ctx, n, ll, lp, lq, pd, f, rho_ptr, step, tile_counter, block_counts, grid_out, adapt, st);
-    return launch_pcn_flow_fused<float>(ctx, n, ll, lp, lq, pd, f, rho_ptr, step, tile_counter, block_counts, grid_out, adapt, st);
+        return launch_pcn_flow_fused<double>(ctx, n, ll, lp, lq, pd, f, rho_ptr, step, tile_counter, block_counts, grid_out, adapt, img_words, st);
+    return launch_pcn_flow_fused<float>(ctx, n, ll, lp, lq, pd, f, rho_ptr, step, tile_counter, block_counts, grid_out, adapt, img_words, st);
 }

@@ -1,5 +1,6 @@
 """Micro-driver of the flow-proposal mutation step (asmc_pcn_mutate_flow) at 1M x 32: timing per step and the per-kernel
-HIP-event table; used under rocprofv3 --pmc by tools/pmc_flowstep.sh.  NOISE=f64|f32, STEPS, N, RHO, ADAPT, KIND=coupling|maf env."""
+HIP-event table; used under rocprofv3 --pmc by tools/pmc_flowstep.sh.  NOISE=f64|f32, STEPS, PROF_STEPS (launches under the HIP events, default 4), N, RHO, ADAPT, KIND=coupling|maf env;
+same-box A/B through ASMC_LIB_PATH, and of the step's two prologues through ASMC_FUSED_STAGE=inline."""
 import os
 import sys
 
@@ -42,7 +43,7 @@ def main():
     torch.cuda.synchronize()
     print(f"noise={noise} n={n}: {e0.elapsed_time(e1) / steps:.4f} ms/step  accept {acc.mean() / n:.3f} rho {rho:.3f}")
     eng.profile(True)
-    eng.pcn_mutate_flow(x, ll, lp, lq, 0.5, mu, eye, inv, t, t, dev, 7, 0, rho0, 4, 40, 0.234, adapt, noise)
+    eng.pcn_mutate_flow(x, ll, lp, lq, 0.5, mu, eye, inv, t, t, dev, 7, 0, rho0, int(os.environ.get("PROF_STEPS", 4)), 40, 0.234, adapt, noise)
     for k, (c, ms) in eng.profile_report().items():
         print(f"   {k:28s} {c:4d} x {ms * 1e3:9.2f} us")
 
