@@ -1288,10 +1288,16 @@ __global__ __launch_bounds__(ASMC_BLOCK) void k_tile_sum(int64_t n, const double
 
 // exclusive scan of tile sums by one block, sequential over chunks of 1024; tiles[] overwritten
 // with the exclusive prefix (+carry); total written to total_out.
+// MONO (the fast cdf's own scan; <false> keeps the bits of the exact mode's hints): the prefixes are the inclusive scan
+// SHIFTED by one tile (never `inc - v`: that is not the exclusive prefix in floating point) behind a running maximum
+// (a Hillis-Steele scan's neighbouring prefixes come from different trees and may fall by a rounding), so
+// carry <= tiles[0] <= tiles[1] <= ... <= total holds for tile sums >= 0: the bounds k_tile_scan clamps its tile into.
+template <bool MONO>
 __global__ __launch_bounds__(1024) void k_scan_tiles(int64_t n_tiles, double* __restrict__ tiles,
                                                     double carry_in, double* __restrict__ total_out,
                                                     const double* __restrict__ carry_dev) {
     __shared__ double s_wave[16];
+    __shared__ double s_max[16];
     __shared__ double s_carry;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) s_carry = carry_dev ? *carry_dev : carry_in;  // (sharded step: the incoming sum is a device-side result)
@@ -1309,16 +1315,43 @@ __global__ __launch_bounds__(1024) void k_scan_tiles(int64_t n_tiles, double* __
         __syncthreads();
         double wp = s_carry;
         for (int k = 0; k < wave; k++) wp += s_wave[k];
-        if (i < n_tiles) tiles[i] = wp + (inc - v);
-        __syncthreads();
-        if (tid == 1023) s_carry = wp + inc;
+        if (MONO) {
+            // inclusive values, then their running maximum over the chunk (comparisons keep a NaN where it is)
+            double m = wp + inc;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const double t = __shfl_up(m, o, 64);
+                if (lane >= o && t > m) m = t;
+            }
+            if (lane == 63) s_max[wave] = m;
+            __syncthreads();
+            double front = s_carry;
+            for (int k = 0; k < wave; k++) front = s_max[k] > front ? s_max[k] : front;
+            if (front > m) m = front;
+            double ex = __shfl_up(m, 1, 64);  // the tile in front's inclusive value = this tile's exclusive prefix
+            if (lane == 0) ex = front;
+            if (i < n_tiles) tiles[i] = ex;
+            __syncthreads();
+            if (tid == 1023) s_carry = m;
+        } else {
+            if (i < n_tiles) tiles[i] = wp + (inc - v);
+            __syncthreads();
+            if (tid == 1023) s_carry = wp + inc;
+        }
         __syncthreads();
     }
     if (tid == 0) *total_out = s_carry;
 }
 
+// Fast cdf, pass 3.  Contract for w >= 0: non-decreasing, cdf[n - 1] == the total bit for bit (so the
+// normalised last element is exactly 1), every element within the derived tolerance of the true prefix sum - relative to the
+// prefix sum itself where a dominant weight follows.  Every exclusive prefix (lane, wave, tile) is a SUM of what lies in
+// front, taken by shifting the inclusive scan, never a difference; a running maximum over the threads' last values repairs
+// the roundings between neighbouring threads' trees; the tile is clamped into [tiles[b], tiles[b + 1]] (the total for the
+// last tile), which chains the tiles; the last element is the total itself.
 __global__ __launch_bounds__(ASMC_BLOCK) void k_tile_scan(int64_t n, const double* __restrict__ w,
                                                          const double* __restrict__ tiles,
+                                                         const double* __restrict__ total_ptr,
                                                          double* __restrict__ cdf,
                                                          const double* __restrict__ norm_ptr) {
     const double norm = norm_ptr ? *norm_ptr : 1.0;
@@ -1339,14 +1372,39 @@ __global__ __launch_bounds__(ASMC_BLOCK) void k_tile_scan(int64_t n, const doubl
         if (lane >= o) inc += t;
     }
     __shared__ double s_wave[ASMC_BLOCK / 64];
+    __shared__ double s_max[ASMC_BLOCK / 64];
     if (lane == 63) s_wave[wave] = inc;
     __syncthreads();
-    double off = tiles[blockIdx.x];
+    const double lo = tiles[blockIdx.x];
+    const double hi = (int64_t)blockIdx.x + 1 < (int64_t)gridDim.x ? tiles[blockIdx.x + 1] : *total_ptr;
+    double off = lo;
     for (int k = 0; k < wave; k++) off += s_wave[k];
-    off += inc - acc;
+    double ex = __shfl_up(inc, 1, 64);  // the sum of the lanes in front
+    if (lane == 0) ex = 0.0;
+    off += ex;
+#pragma unroll
+    for (int j = 0; j < SC_E; j++) v[j] = off + v[j];
+    // running maximum of the threads' last values, exclusive: what no element of this thread may fall below
+    double m = v[SC_E - 1];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double t = __shfl_up(m, o, 64);
+        if (lane >= o && t > m) m = t;
+    }
+    if (lane == 63) s_max[wave] = m;
+    __syncthreads();
+    double floor_v = __shfl_up(m, 1, 64);
+    if (lane == 0) floor_v = lo;
+    for (int k = 0; k < wave; k++) floor_v = s_max[k] > floor_v ? s_max[k] : floor_v;
 #pragma unroll
     for (int j = 0; j < SC_E; j++)
-        if (base + j < n) cdf[base + j] = (off + v[j]) / norm;
+        if (base + j < n) {
+            double x = v[j];
+            x = x < floor_v ? floor_v : x;
+            x = x > hi ? hi : x;
+            if (base + j == n - 1) x = *total_ptr;
+            cdf[base + j] = x / norm;
+        }
 }
 
 // divisor read from the device (the total the preceding cdf pass left there): no host round trip
@@ -1523,7 +1581,9 @@ __global__ __launch_bounds__(ASMC_BLOCK) void k_search(int64_t n, const double* 
             else
                 hi = mid;
         }
-        idx[j] = lo;
+        // a key below 1 names a row: a cdf whose last element fell below the key (an unnormalised one, a rounding) must not
+        // send n to the gather (k_search_pcg's clamp).  Keys >= 1 keep numpy's answer n; a NaN key gives 0 (no cdf[k] <= NaN)
+        idx[j] = (lo >= n && key < 1.0) ? n - 1 : lo;
     }
 }
 
@@ -1572,7 +1632,8 @@ __global__ __launch_bounds__(ASMC_BLOCK) void k_search_guided(int64_t n, const d
             else
                 hi = mid;
         }
-        idx[j] = lo;
+        // (the clamp of k_search, for the same reason)
+        idx[j] = (lo >= n && key < 1.0) ? n - 1 : lo;
     }
 }
 
@@ -1999,7 +2060,7 @@ int asmc_cdf(asmc_ctx* ctx, int64_t n, const double* w, double* cdf, int mode, d
         double* d_approx_total = ctx->d_small + 1025;
         ASMC_LAUNCH(ctx, st, "k_tile_sum", k_tile_sum, dim3((unsigned)n_tiles), dim3(ASMC_BLOCK), 0, st, n, w, ctx->d_tiles);
         ASMC_LAUNCH_CHECK();
-        ASMC_LAUNCH(ctx, st, "k_scan_tiles", k_scan_tiles, dim3(1), dim3(1024), 0, st, n_tiles, ctx->d_tiles, carry_in, d_approx_total, (const double*)nullptr);
+        ASMC_LAUNCH(ctx, st, "k_scan_tiles", k_scan_tiles<false>, dim3(1), dim3(1024), 0, st, n_tiles, ctx->d_tiles, carry_in, d_approx_total, (const double*)nullptr);
         ASMC_LAUNCH_CHECK();
         ASMC_LAUNCH(ctx, st, "k_exact_tile_td_launch", k_exact_tile_td_launch, dim3((unsigned)n_tiles), dim3(XT_THREADS), 0, st, n, w,
                            (const double*)ctx->d_tiles, (const double*)d_approx_total, n_tiles, ctx->d_tiles_i, d_split,
@@ -2017,10 +2078,10 @@ int asmc_cdf(asmc_ctx* ctx, int64_t n, const double* w, double* cdf, int mode, d
         const int64_t n_tiles = (n + ASMC_SCAN_TILE - 1) / ASMC_SCAN_TILE;
         ASMC_LAUNCH(ctx, st, "k_tile_sum", k_tile_sum, dim3((unsigned)n_tiles), dim3(ASMC_BLOCK), 0, st, n, w, ctx->d_tiles);
         ASMC_LAUNCH_CHECK();
-        ASMC_LAUNCH(ctx, st, "k_scan_tiles", k_scan_tiles, dim3(1), dim3(1024), 0, st, n_tiles, ctx->d_tiles, carry_in, d_total, (const double*)nullptr);
+        ASMC_LAUNCH(ctx, st, "k_scan_tiles", k_scan_tiles<true>, dim3(1), dim3(1024), 0, st, n_tiles, ctx->d_tiles, carry_in, d_total, (const double*)nullptr);
         ASMC_LAUNCH_CHECK();
         ASMC_LAUNCH(ctx, st, "k_tile_scan", k_tile_scan, dim3((unsigned)n_tiles), dim3(ASMC_BLOCK), 0, st, n, w,
-                           (const double*)ctx->d_tiles, cdf, d_norm);
+                           (const double*)ctx->d_tiles, (const double*)d_total, cdf, d_norm);
         ASMC_LAUNCH_CHECK();
     } else {
         asmc_set_error("asmc_cdf: unknown mode %d", mode);
@@ -2046,7 +2107,7 @@ static int cdf_shard_records_impl(asmc_ctx* ctx, int64_t n, const double* w, dou
     double* d_approx_total = ctx->d_small + 1025;
     ASMC_LAUNCH(ctx, st, "k_tile_sum", k_tile_sum, dim3((unsigned)n_tiles), dim3(ASMC_BLOCK), 0, st, n, w, ctx->d_tiles);
     ASMC_LAUNCH_CHECK();
-    ASMC_LAUNCH(ctx, st, "k_scan_tiles", k_scan_tiles, dim3(1), dim3(1024), 0, st, n_tiles, ctx->d_tiles,
+    ASMC_LAUNCH(ctx, st, "k_scan_tiles", k_scan_tiles<false>, dim3(1), dim3(1024), 0, st, n_tiles, ctx->d_tiles,
                 first_rank ? 0.0 : approx_carry, d_approx_total, first_rank ? (const double*)nullptr : approx_carry_dev);
     ASMC_LAUNCH_CHECK();
     ASMC_LAUNCH(ctx, st, "k_exact_tile_td_launch", k_exact_tile_td_launch, dim3((unsigned)n_tiles), dim3(XT_THREADS), 0, st, n, w,
@@ -2401,7 +2462,7 @@ int asmc_importance_step(asmc_ctx* ctx, int64_t n, const double* ll, const doubl
                     (const double*)w_scratch, (const double*)ctx->d_tiles, n_tiles, ctx->d_tiles_i, d_split, d_tile_s2,
                     cdf_scratch, d_tile_s);
     } else {
-        ASMC_LAUNCH(ctx, st, "k_scan_tiles", k_scan_tiles, dim3(1), dim3(1024), 0, st, n_tiles, ctx->d_tiles, 0.0, ctx->d_small + 1025, (const double*)nullptr);
+        ASMC_LAUNCH(ctx, st, "k_scan_tiles", k_scan_tiles<false>, dim3(1), dim3(1024), 0, st, n_tiles, ctx->d_tiles, 0.0, ctx->d_small + 1025, (const double*)nullptr);
         ASMC_LAUNCH_CHECK();
         ASMC_LAUNCH(ctx, st, "k_exact_tile_td_launch", k_exact_tile_td_launch, dim3((unsigned)n_tiles), dim3(XT_THREADS), 0, st, n,
                     (const double*)w_scratch, (const double*)ctx->d_tiles, (const double*)(ctx->d_small + 1025), n_tiles,

@@ -303,14 +303,25 @@ int asmc_count_nonfinite(asmc_ctx* ctx, int64_t n, const double* v_dev, int64_t*
  * asmc_cdf: inclusive cumulative sum of w, carry_in added in front (rank chaining).
  *   mode ASMC_CDF_EXACT reproduces the *sequential* fp64 accumulation of numpy's cumsum
  *   bit-for-bit (parallelised through round-to-nearest-even integer transducers);
- *   ASMC_CDF_FAST uses a parallel scan order.  total_host receives the last element.
+ *   ASMC_CDF_FAST uses a parallel scan order.  Its contract for w >= 0: non-decreasing, the last
+ *   element equal to the total bit for bit (so the normalised last element is exactly 1), every element within
+ *   A u / (1 - A u) of the true prefix sum relative to that sum itself, A = 43 + 16 (ceil(n / 2^21) - 1), u = 2^-53.
+ *   total_host receives the last element.  A total of 0 (or a non-finite one) normalises to NaN everywhere, in both modes.
+ *   Weights below 0 are outside the contract: the fast mode's running maxima and clamps then no longer return the plain
+ *   cumulative sum (a decrease is flattened); ASMC_CDF_EXACT remains numpy's cumsum for any sign.
  * asmc_cdf_normalize: cdf /= last    (numpy: cdf /= cdf[-1]).
  * asmc_cdf_normalize_last: the same with the total the preceding asmc_cdf on this ctx left on the device
  *   (call asmc_cdf with total_host = NULL: no host round trip between the scan and the division).
  * asmc_pcg64_uniforms: u[j] = j-th next double of numpy's PCG64 stream given its raw state
  *   {state_hi, state_lo, inc_hi, inc_lo} after skipping `offset` draws (the host then calls
  *   bit_generator.advance(n)).
- * asmc_search: idx[j] = #{k : cdf[k] <= u[j]}  == cdf.searchsorted(u, side="right").
+ * asmc_search: idx[j] = #{k : cdf[k] <= u[j]}  == cdf.searchsorted(u, side="right"), with two deviations that keep every
+ *   key below 1 inside the rows (the result goes to asmc_gather unclamped):
+ *     - a key u < 1 never gives n: where the cdf ends below the key (an unnormalised cdf, a cdf that is not a cdf) the answer
+ *       is n - 1.  On a normalised cdf (last element 1) this never acts;
+ *     - a NaN key gives 0 (no cdf[k] <= NaN); numpy sorts NaN last and answers n.
+ *   Keys >= 1 (1.0, +inf) give n as numpy does, keys below cdf[0] (negative ones, -0.0 counts as 0.0) give 0.  The cdf must be
+ *   non-decreasing; both cdf modes guarantee that for w >= 0.
  * asmc_gather: x_out[j,:] = x_in[idx[j],:] and the three scalar vectors (samples.py:1279-1287). */
 int asmc_cdf(asmc_ctx* ctx, int64_t n, const double* w_dev, double* cdf_dev, int mode,
              double carry_in, double* total_host, asmc_stream stream);
