@@ -164,7 +164,7 @@ struct asmc_ctx {
     long long prof_vcnt[ASMC_PROF_VARIANTS];    // and launches
     // pinned host staging for scalar read-back / small uploads
     double* h_pinned;  // [8192] doubles
-    unsigned ref_status_gen;  // asmc_reference_factor: generation of the pinned status cell in use (asmc_pcn.hip)
+    unsigned ref_status_gen;  // asmc_reference_factor: generation of the pinned status cell in use (asmc_moments.hip)
     double* h_gram;    // [128 + 128 * 128] doubles: asmc_mean_gram's results (sum | Gram) until asmc_mean_gram_fetch
     double* d_ref;     // the same on the device (d_small / d_partials are every other call's scratch): asmc_reference_factor
     int gram_pending_d;  // d of an enqueued, not yet fetched asmc_mean_gram (0: none)
@@ -188,7 +188,7 @@ bool asmc_pcn_flow16_ok(const asmc_pcn_params* prm, const asmc_coupling* f);
 bool asmc_flow_math_split();
 
 // asmc_weights.hip: the persistent weight kernel of asmc_importance_step (results in ctx->d_small + 2560 .. + 48)
-// k_ref_factor on the stream (asmc_pcn.hip; asmc_reference_factor and the Student-t EM of asmc_student.hip)
+// k_ref_factor on the stream (asmc_moments.hip; asmc_reference_factor and the Student-t EM of asmc_student.hip)
 int asmc_ref_factor_launch(asmc_ctx* ctx, int d, const double* sum, const double* gram, double n_mean, double denom, double* out,
                            double* status, double* tab, double* em, int it, hipStream_t st);
 int asmc_gram_mm_launch(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, const double* d_center, int* grid_out,

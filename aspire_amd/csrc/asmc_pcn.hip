@@ -1,4 +1,6 @@
-// asmc_pcn.hip — proposal draw, built-in densities, population moments, pCN mutation.
+// asmc_pcn.hip — pCN mutation: the step kernels, their host drivers, the zero-padding scheme.
+// (The proposal draw and the built-in densities live in asmc_density.hip, the population moments and the reference fit in
+// asmc_moments.hip; asmc_pcn_shared.h holds what they share with this file.)
 //
 // Replaces (reference mj-will/aspire):
 //   src/aspire/samplers/smc/minipcn.py:69-135  MiniPCNSMC.mutate  (wraps third-party minipcn —
@@ -6,7 +8,6 @@
 //       specification; parity with minipcn is unpinned)
 //   src/aspire/samplers/smc/base.py:507-519 + src/aspire/samples.py:1217-1219  tempered target
 //       log p_t = (1-beta) log_q + beta (log_likelihood + log_prior) [+ log|J|], NaN -> -inf
-//   src/aspire/samplers/mcmc.py:66-67  flow.sample_and_log_prob for the analytic Gaussian proposal
 //
 // Data movement: particle rows (d*s bytes, particle-major) are fetched with fully coalesced
 // 16-B-per-lane loads into a padded LDS tile (64 rows per wave, row stride = rowbytes + 16 so that
@@ -17,42 +18,8 @@
 
 #include <chrono>
 
-#include "asmc_common.h"
-#include "asmc_tile.h"
-#include "asmc_pcn_dev.h"
+#include "asmc_pcn_shared.h"
 #include "asmc_transform_dev.h"
-
-// =============================================================================================
-// LDS row tiles
-// =============================================================================================
-// diagonal-mixture log-density of the row stored (as T) at `row`
-template <typename T>
-__device__ __forceinline__ double mixture_eval(const MixDev& m, int d, const char* row) {
-    double best = -INFINITY;
-    double terms[ASMC_MAX_COMPONENTS];
-    const int C = m.C;
-    for (int c = 0; c < C; c++) {
-        double q = 0.0;
-        const double* mu = m.mu + (size_t)c * d;
-        const double* pr = m.prec + (size_t)c * d;
-        for (int j = 0; j < d; j++) {
-            const double t = row_get<T>(row, j) - mu[j];
-            q = fma(t * t, pr[j], q);
-        }
-        const double v = m.logw[c] - 0.5 * q;
-        terms[c] = v;
-        best = fmax(best, v);
-    }
-    if (C == 1) return terms[0];
-    if (best == -INFINITY) {  // every term -inf or NaN (fmax skips a NaN): their sum - -inf, or NaN for a row with a NaN coordinate
-        double t = 0.0;
-        for (int c = 0; c < C; c++) t += terms[c];
-        return t;
-    }
-    double s = 0.0;
-    for (int c = 0; c < C; c++) s += exp(terms[c] - best);
-    return best + log(s);
-}
 
 // =============================================================================================
 // fused pCN step, generic in d: per-lane work vector v[k] lives in LDS (SoA: v[k*64 + lane])
@@ -295,12 +262,6 @@ __device__ __forceinline__ void tri_matvec_inplace(const double* __restrict__ A,
 #pragma unroll
         for (int r = 0; r < RG; r++) v[j0 + r] = s[r];
     }
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-    // each wave owns its LDS tile: ordering within the wave is enough (no s_barrier, waves run decoupled)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
 }
 
 // MODE 0: one pCN step on x (whiten, propose, un-whiten, evaluate, accept)            — any built-in target
@@ -1149,344 +1110,8 @@ static int launch_copy_flagged(asmc_ctx* ctx, int64_t n, int d, int x_dtype, voi
 }
 
 // =============================================================================================
-// analytic Gaussian proposal draw, built-in density evaluation
-// =============================================================================================
-template <typename T>
-__global__ __launch_bounds__(ASMC_BLOCK) void k_gaussian_draw(int64_t n, int d, const double* __restrict__ mu,
-                                                             const double* __restrict__ sigma,
-                                                             unsigned long long seed, unsigned long long gid0,
-                                                             uint32_t draw_id, T* __restrict__ x,
-                                                             const double* __restrict__ bmtab) {
-    bm_d2* bmt = bm_lds();
-    bm_tab_stage<ASMC_BLOCK>(bmt, bmtab);
-    __syncthreads();
-    const int quads = (d + 3) / 4;  // one Philox block = four coordinates (asmc_pcn_dev.h normal_quad)
-    const int64_t total = n * quads;
-    const int64_t stride = (int64_t)gridDim.x * ASMC_BLOCK;
-    for (int64_t e = (int64_t)blockIdx.x * ASMC_BLOCK + threadIdx.x; e < total; e += stride) {
-        const int64_t i = e / quads;
-        const int qd = (int)(e - i * quads);
-        double z[4];
-        normal_quad(seed, gid0 + (unsigned long long)i, draw_id, (uint32_t)qd, bmt, z[0], z[1], z[2], z[3]);
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const int j = 4 * qd + c;
-            if (j < d) x[i * d + j] = (T)fma(sigma[j], z[c], mu[j]);
-        }
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(ASMC_BLOCK) void k_gaussian_logq(int64_t n, int d, const double* __restrict__ mu,
-                                                             const double* __restrict__ sigma,
-                                                             const T* __restrict__ x, double* __restrict__ lq) {
-    const int64_t stride = (int64_t)gridDim.x * ASMC_BLOCK;
-    for (int64_t i = (int64_t)blockIdx.x * ASMC_BLOCK + threadIdx.x; i < n; i += stride) {
-        double q = 0.0, ls = 0.0;
-        for (int j = 0; j < d; j++) {
-            const double z = ((double)x[i * d + j] - mu[j]) / sigma[j];
-            q = fma(z, z, q);
-            ls += log(sigma[j]);
-        }
-        lq[i] = -0.5 * q - ls - 0.5 * (double)d * 1.8378770664093454835606594728112;  // log(2 pi)
-    }
-}
-
-template <typename T, int VEC>
-__global__ __launch_bounds__(ASMC_BLOCK) void k_mixture_logpdf(int64_t n, int d, const T* __restrict__ x,
-                                                              MixDev m, double* __restrict__ out,
-                                                              int waves_per_block) {
-    extern __shared__ __align__(16) char smem[];
-    const int rowbytes = d * (int)sizeof(T);
-    const int ldsrow = lds_row_stride(rowbytes);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    char* tile = smem + (size_t)wave * 64 * ldsrow;
-    const int64_t n_tiles = (n + 63) / 64;
-    for (int64_t tile0 = (int64_t)blockIdx.x * waves_per_block; tile0 < n_tiles;
-         tile0 += (int64_t)gridDim.x * waves_per_block) {
-        const int64_t t = tile0 + wave;
-        const bool active = t < n_tiles;
-        const int64_t i = t * 64 + lane;
-        const int64_t row0 = t * 64;
-        const int64_t valid_bytes = active ? (((n - row0) < 64 ? (n - row0) : 64) * (int64_t)rowbytes) : 0;
-        if (active) tile_load<VEC>(reinterpret_cast<const char*>(x) + row0 * rowbytes, valid_bytes, rowbytes, ldsrow, tile, lane);
-        __syncthreads();
-        if (active && i < n) out[i] = mixture_eval<T>(m, d, tile + lane * ldsrow);
-        __syncthreads();
-    }
-}
-
-// Flat form for rows of a power-of-two number (<= 64) of 16-byte pieces: one piece per thread, coalesced 16-byte loads with
-// no LDS, the piece's coordinates' (mu, prec) of every component in registers for the whole grid-stride loop, quadratic forms
-// completed by a butterfly over the row's lanes, log-sum-exp over the components by the row's first lane (same formula as
-// mixture_eval; the quadratic form is summed in butterfly order instead of coordinate order: ~1e-16 relative).
-template <typename T, int CMAX>
-__global__ __launch_bounds__(ASMC_BLOCK) void k_mixture_flat(int64_t n, int d, int tpr_log2, const uint4* __restrict__ x, MixDev m,
-                                                            double* __restrict__ out, const double* __restrict__ premap) {
-    // premap != NULL (asmc_mixture_logpdf_premap): the density is evaluated at t_j = clip(a_j x_j + b_j, lo_j, hi_j) and
-    // sum_j h_j t_j^2 is added; rows a, b, lo, hi, h of d doubles each
-    constexpr int EPT = 16 / (int)sizeof(T);
-    const int tpr = 1 << tpr_log2, C = m.C;
-    const int64_t total = n << tpr_log2;
-    const int64_t stride = (int64_t)gridDim.x * ASMC_BLOCK;  // a multiple of tpr: a thread keeps its coordinates
-    const int c0 = (int)(((int64_t)blockIdx.x * ASMC_BLOCK + threadIdx.x) & (tpr - 1));
-    double mu[CMAX][EPT], pr[CMAX][EPT];
-#pragma unroll
-    for (int c = 0; c < CMAX; c++)
-#pragma unroll
-        for (int k = 0; k < EPT; k++) {
-            mu[c][k] = c < C ? m.mu[(size_t)c * d + c0 * EPT + k] : 0.0;
-            pr[c][k] = c < C ? m.prec[(size_t)c * d + c0 * EPT + k] : 0.0;
-        }
-    double pa[EPT], pb[EPT], plo[EPT], phi[EPT], ph[EPT];
-#pragma unroll
-    for (int k = 0; k < EPT; k++) {
-        const int j = c0 * EPT + k;
-        pa[k] = premap ? premap[j] : 1.0;
-        pb[k] = premap ? premap[d + j] : 0.0;
-        plo[k] = premap ? premap[2 * d + j] : -INFINITY;
-        phi[k] = premap ? premap[3 * d + j] : INFINITY;
-        ph[k] = premap ? premap[4 * d + j] : 0.0;
-    }
-    for (int64_t e0 = (int64_t)blockIdx.x * ASMC_BLOCK + threadIdx.x; e0 - (threadIdx.x & 63) < total; e0 += stride) {
-        const bool valid = e0 < total;
-        double q[CMAX], extra = 0.0;
-#pragma unroll
-        for (int c = 0; c < CMAX; c++) q[c] = 0.0;
-        if (valid) {
-            const uint4 raw = x[e0];
-            const T* vals = reinterpret_cast<const T*>(&raw);
-            double xv[EPT];
-#pragma unroll
-            for (int k = 0; k < EPT; k++) {
-                xv[k] = (double)vals[k];
-                if (premap) {
-                    xv[k] = clip(xv[k] * pa[k] + pb[k], plo[k], phi[k]);  // (NaN stays NaN: fmin / fmax would hand out a clamp end)
-                    extra = fma(ph[k] * xv[k], xv[k], extra);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < CMAX; c++)
-#pragma unroll
-                for (int k = 0; k < EPT; k++) {
-                    const double t = xv[k] - mu[c][k];
-                    q[c] = fma(t * t, pr[c][k], q[c]);
-                }
-        }
-#pragma unroll
-        for (int c = 0; c < CMAX; c++)
-            for (int o = tpr >> 1; o >= 1; o >>= 1) q[c] += __shfl_xor(q[c], o, 64);
-        if (premap)
-            for (int o = tpr >> 1; o >= 1; o >>= 1) extra += __shfl_xor(extra, o, 64);
-        if (valid && c0 == 0) {
-            double best = -INFINITY, terms[CMAX];
-#pragma unroll
-            for (int c = 0; c < CMAX; c++) {
-                terms[c] = c < C ? m.logw[c] - 0.5 * q[c] : -INFINITY;
-                best = fmax(best, terms[c]);
-            }
-            double r = terms[0];
-            if (C > 1) {
-                if (best == -INFINITY) {  // every term -inf or NaN: their sum (mixture_eval)
-                    r = 0.0;
-#pragma unroll
-                    for (int c = 0; c < CMAX; c++)
-                        if (c < C) r += terms[c];
-                } else {
-                    double ssum = 0.0;
-#pragma unroll
-                    for (int c = 0; c < CMAX; c++)
-                        if (c < C) ssum += exp(terms[c] - best);
-                    r = best + log(ssum);
-                }
-            }
-            out[e0 >> tpr_log2] = r + extra;
-        }
-    }
-}
-
-
-// =============================================================================================
-// population moments
-// =============================================================================================
-template <typename T>
-__global__ __launch_bounds__(ASMC_BLOCK) void k_colsum(int64_t n, int d, const T* __restrict__ x,
-                                                      double* __restrict__ partials) {
-    // thread t owns column (t % d) when ASMC_BLOCK % d == 0, otherwise a strided element walk with
-    // per-element column lookup; partial sums are combined through LDS atomics-free reduction.
-    extern __shared__ __align__(16) char smem[];
-    double* s_acc = reinterpret_cast<double*>(smem);  // [ASMC_BLOCK]
-    const int rows_per_pass = ASMC_BLOCK / d;         // >= 1 (d <= 256)
-    const int my_col = threadIdx.x % d;
-    const int my_sub = threadIdx.x / d;
-    double acc = 0.0;
-    if (my_sub < rows_per_pass) {
-        for (int64_t r = (int64_t)blockIdx.x * rows_per_pass + my_sub; r < n; r += (int64_t)gridDim.x * rows_per_pass)
-            acc += (double)x[r * d + my_col];
-    }
-    s_acc[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x < d) {
-        double v = 0.0;
-        for (int s = 0; s < rows_per_pass; s++) v += s_acc[s * d + threadIdx.x];
-        partials[(size_t)blockIdx.x * d + threadIdx.x] = v;
-    }
-}
-
-// gram partial: G[j,k] += (x_ij - c_j)(x_ik - c_k) over the block's rows; tile of 64 centred rows in LDS
-template <typename T>
-__global__ __launch_bounds__(ASMC_BLOCK) void k_gram(int64_t n, int d, const T* __restrict__ x,
-                                                    const double* __restrict__ center,
-                                                    double* __restrict__ partials) {
-    extern __shared__ __align__(16) char smem[];
-    double* s_rows = reinterpret_cast<double*>(smem);  // [64][d+1]
-    const int ld = d + 1;
-    const int dd = d * d;
-    // entries e = tid, tid+256, ... (< d*d <= 4096): at most 16 accumulators per thread
-    double acc[16];
-    int jj[16], kk[16];
-#pragma unroll
-    for (int a = 0; a < 16; a++) {
-        acc[a] = 0.0;
-        const int e = threadIdx.x + a * ASMC_BLOCK;
-        const int ec = e < dd ? e : 0;
-        jj[a] = ec / d;
-        kk[a] = ec - jj[a] * d;
-    }
-    for (int64_t row0 = (int64_t)blockIdx.x * 64; row0 < n; row0 += (int64_t)gridDim.x * 64) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < 64 * d; e += ASMC_BLOCK) {
-            const int r = e / d, c = e - r * d;
-            const int64_t gr = row0 + r;
-            s_rows[r * ld + c] = gr < n ? (double)x[gr * d + c] - center[c] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int r = 0; r < 64; r++) {
-            const double* row = s_rows + r * ld;
-#pragma unroll
-            for (int a = 0; a < 16; a++)
-                if (a * ASMC_BLOCK < dd) acc[a] = fma(row[jj[a]], row[kk[a]], acc[a]);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 16; a++) {
-        const int e = threadIdx.x + a * ASMC_BLOCK;
-        if (e < dd) partials[(size_t)blockIdx.x * dd + e] = acc[a];
-    }
-}
-
-// Register-blocked centred Gram matrix: one wave owns a (8*BLK) x (8*BLK) quadrant of G, lane (bi, bj) a
-// BLK x BLK block of it (16 or 64 accumulators in VGPRs).  Rows are staged 64 at a time through the wave's
-// LDS tile with coalesced 16-B loads; per row every lane reads two BLK-wide slices (same row for all lanes:
-// LDS broadcast, conflict free) and issues BLK^2 FMAs — 0.5 (BLK=4) / 0.25 (BLK=8) LDS reads per FMA.
-// blockIdx.y selects the quadrant (d > 8*BLK needs several).  Block partial [d_pad x d_pad] per block.
-template <typename T, int BLK>
-__global__ __launch_bounds__(ASMC_BLOCK) void k_gram_rb(int64_t n, int d, const T* __restrict__ x,
-                                                       const double* __restrict__ center,
-                                                       double* __restrict__ partials, int n_quad_side) {
-    extern __shared__ __align__(16) char smem[];
-    constexpr int Q = 8 * BLK;  // quadrant side
-    const int rowbytes = d * (int)sizeof(T);
-    const int ldsrow = lds_row_stride(rowbytes);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    char* tile = smem + (size_t)wave * 64 * ldsrow;
-    const int qi = blockIdx.y / n_quad_side, qj = blockIdx.y % n_quad_side;
-    const int bi = lane >> 3, bj = lane & 7;
-    const int i0 = qi * Q + bi * BLK, j0 = qj * Q + bj * BLK;  // first row / column of this lane's block
-    double ci[BLK], cj[BLK], acc[BLK][BLK];
-#pragma unroll
-    for (int a = 0; a < BLK; a++) {
-        ci[a] = (i0 + a < d) ? center[i0 + a] : 0.0;
-        cj[a] = (j0 + a < d) ? center[j0 + a] : 0.0;
-#pragma unroll
-        for (int b = 0; b < BLK; b++) acc[a][b] = 0.0;
-    }
-    const int64_t n_tiles = (n + 63) / 64;
-    const int wpb = (int)(blockDim.x >> 6);
-    for (int64_t t = (int64_t)blockIdx.x * wpb + wave; t < n_tiles; t += (int64_t)gridDim.x * wpb) {
-        const int64_t row0 = t * 64;
-        const int rows = (int)((n - row0) < 64 ? (n - row0) : 64);
-        wave_lds_sync();
-        tile_load<16>(reinterpret_cast<const char*>(x) + row0 * rowbytes, (int64_t)rows * rowbytes, rowbytes, ldsrow, tile, lane);
-        wave_lds_sync();
-        for (int r = 0; r < rows; r++) {
-            const T* row = reinterpret_cast<const T*>(tile + r * ldsrow);
-            double ai[BLK], aj[BLK];
-#pragma unroll
-            for (int a = 0; a < BLK; a++) {
-                ai[a] = (i0 + a < d) ? (double)row[i0 + a] - ci[a] : 0.0;
-                aj[a] = (j0 + a < d) ? (double)row[j0 + a] - cj[a] : 0.0;
-            }
-#pragma unroll
-            for (int a = 0; a < BLK; a++)
-#pragma unroll
-                for (int b = 0; b < BLK; b++) acc[a][b] = fma(ai[a], aj[b], acc[a][b]);
-        }
-    }
-    // combine the block's waves through LDS (fixed order), write the block partial of this quadrant
-    __syncthreads();
-    double* red = reinterpret_cast<double*>(smem);  // [wpb][Q*Q] fits: Q*Q*8 <= 64*ldsrow for d >= Q/2
-    double* mine = red + (size_t)wave * Q * Q;
-#pragma unroll
-    for (int a = 0; a < BLK; a++)
-#pragma unroll
-        for (int b = 0; b < BLK; b++) mine[(bi * BLK + a) * Q + bj * BLK + b] = acc[a][b];
-    __syncthreads();
-    const int dpad = n_quad_side * Q;
-    for (int e = threadIdx.x; e < Q * Q; e += (int)blockDim.x) {
-        double v = red[e];
-        for (int w = 1; w < wpb; w++) v += red[(size_t)w * Q * Q + e];
-        const int gi = qi * Q + e / Q, gj = qj * Q + e % Q;
-        partials[(size_t)blockIdx.x * dpad * dpad + (size_t)gi * dpad + gj] = v;
-    }
-}
-
-// one block per column; 64 threads (one wave: the order every caller has always had) or 256 (the gather's column-sum partials:
-// 4 096 rows - 24 us with one wave): strided partial sums, the wave's butterfly, then the waves in order
-// keep / center (optional): the sum also goes to keep[col] (the copy asmc_reference_factor reads in ctx->d_ref) and
-// center[col] = sum / n_mean (k_center_from_sum's division)
-__global__ __launch_bounds__(256) void k_reduce_columns(int nblocks, int ncols, const double* __restrict__ partials,
-                                                       double* __restrict__ out, double* __restrict__ keep = nullptr,
-                                                       double* __restrict__ center = nullptr, double n_mean = 1.0) {
-    __shared__ double s_w[4];
-    const int nt = (int)blockDim.x;
-    for (int col = blockIdx.x; col < ncols; col += gridDim.x) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < nblocks; b += nt) v += partials[(size_t)b * ncols + col];
-        v = wave_sum(v);
-        if (nt != 64) {
-            if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-            __syncthreads();
-            v = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            out[col] = v;
-            if (keep) keep[col] = v;
-            if (center) center[col] = v / n_mean;
-        }
-    }
-}
-
-// =============================================================================================
 // host side
 // =============================================================================================
-static int pick_vec(int rowbytes, const void* p0, const void* p1) {
-    const uintptr_t a = (uintptr_t)p0 | (uintptr_t)p1;
-    if (rowbytes % 16 == 0 && a % 16 == 0) return 16;
-    if (rowbytes % 8 == 0 && a % 8 == 0) return 8;
-    return 4;
-}
-
-static int waves_for_lds(size_t per_wave_bytes, size_t* lds_bytes_out) {
-    const size_t budget = 160 * 1024 - 1024 - BM_TAB_N * 16;  // (the block's Box-Muller tables sit next to the tiles)
-    int w = ASMC_BLOCK / 64;
-    while (w > 1 && per_wave_bytes * (size_t)w > budget) w >>= 1;
-    *lds_bytes_out = per_wave_bytes * (size_t)w;
-    return w;
-}
-
 // gather the caller's tables into the ctx parameter block (one tiny kernel, stream ordered)
 __global__ __launch_bounds__(256) void k_pcn_pack(PcnDev pd, double* __restrict__ t, double* __restrict__ rho_cell, double rho) {
     if (rho_cell && threadIdx.x == 0) *rho_cell = rho;  // (the call's starting step size rides along: no k_set_scalar launch)
@@ -1534,7 +1159,57 @@ static int pack_pcn_tables(asmc_ctx* ctx, const PcnDev& pd, hipStream_t st, doub
 
 static bool pcn_reg_supported(int d, size_t elem, const void* x) {
     return (d == 4 || d == 8 || d == 16 || d == 32) && (d * elem) % 16 == 0 && ((uintptr_t)x % 16) == 0 &&
-           !getenv("ASMC_PCN_GENERIC");
+           !pcn_env_generic();
+}
+
+// A call's parameters as the kernels take them: the reference, the tempering and the noise keys.  The densities and the noise
+// mode are the caller's to add - a flow mutation carries a placeholder for log q, a split session no density at all, and each
+// entry point checks the noise mode under its own name.  Everything else starts at zero (mode: PCN_X_STEP).
+static PcnDev pcn_dev_from_params(const asmc_ctx* ctx, const asmc_pcn_params* prm, int d_noise) {
+    PcnDev pd;
+    memset(&pd, 0, sizeof(pd));
+    pd.bmtab = ctx->d_bmtab;
+    pd.d = prm->d;
+    pd.d_noise = d_noise;
+    pd.beta = prm->beta;
+    pd.mu = prm->mu_dev;
+    pd.L = prm->L_dev;
+    pd.Linv = prm->Linv_dev;
+    pd.seed = prm->seed;
+    pd.gid0 = prm->gid0;
+    pd.nu = prm->nu;
+    return pd;
+}
+
+// the by-value part of a launch's parameters (the tables travel in ctx->d_ptab)
+static PcnScalars pcn_scalars(const PcnDev& pd) {
+    PcnScalars ps;
+    ps.beta = pd.beta;
+    ps.nu = pd.nu;
+    ps.gam = pd.gam;
+    ps.ys = pd.ys;
+    ps.n_pad = pd.n_pad;
+    ps.d_real = pd.d;
+    ps.seed = pd.seed;
+    ps.gid0 = pd.gid0;
+    ps.bmtab = pd.bmtab;
+    ps.tile_par = pd.tile_par;
+    ps.d_noise = pd.d_noise;
+    ps.c_ll = pd.ll.C;
+    ps.c_lp = pd.lp.C;
+    ps.c_lq = pd.lq.C;
+    return ps;
+}
+
+// the profile label of k_pcn_reg's modes
+static constexpr const char* pcn_reg_label(int mode) {
+    return mode == PCN_X_STEP ? "k_pcn_reg"
+           : (mode == PCN_Y_STEP || mode == PCN_Y_STEP_S || mode == PCN_Y_STEP_SG) ? "k_pcn_reg_y"
+           : mode == PCN_X_STEP_T ? "k_tpcn_reg"
+           : (mode == PCN_Y_STEP_T || mode == PCN_Y_STEP_TS || mode == PCN_Y_STEP_TSG) ? "k_tpcn_reg_y"
+           : (mode == PCN_WHITEN || mode == PCN_WHITEN_S) ? "k_pcn_whiten"
+           : (mode >= PCN_X_PROPOSE && mode <= PCN_X_PROPOSE_PAD_T) ? "k_pcn_propose_reg"
+                                                                    : "k_pcn_unwhiten";
 }
 
 template <typename T, int D, int NOISE, int MODE>
@@ -1566,23 +1241,9 @@ static int launch_pcn_reg(asmc_ctx* ctx, int64_t n, T* x, double* ll, double* lp
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         attr_set = true;
     }
-    PcnScalars ps;
-    ps.beta = pd.beta;
-    ps.nu = pd.nu;
-    ps.gam = pd.gam;
-    ps.ys = pd.ys;
-    ps.n_pad = pd.n_pad;
-    ps.d_real = pd.d;
-    ps.seed = pd.seed;
-    ps.gid0 = pd.gid0;
-    ps.bmtab = pd.bmtab;
-    ps.tile_par = pd.tile_par;
-    ps.d_noise = pd.d_noise;
-    ps.c_ll = pd.ll.C;
-    ps.c_lp = pd.lp.C;
-    ps.c_lq = pd.lq.C;
-    ASMC_LAUNCH(ctx, st, MODE == PCN_X_STEP ? "k_pcn_reg" : (MODE == PCN_Y_STEP || MODE == PCN_Y_STEP_S || MODE == PCN_Y_STEP_SG) ? "k_pcn_reg_y" : MODE == PCN_X_STEP_T ? "k_tpcn_reg" : (MODE == PCN_Y_STEP_T || MODE == PCN_Y_STEP_TS || MODE == PCN_Y_STEP_TSG) ? "k_tpcn_reg_y" : (MODE == PCN_WHITEN || MODE == PCN_WHITEN_S) ? "k_pcn_whiten" : (MODE >= PCN_X_PROPOSE && MODE <= PCN_X_PROPOSE_PAD_T) ? "k_pcn_propose_reg" : "k_pcn_unwhiten", kern, dim3(grid), dim3(wpb * 64), lds_bytes, st, n, x, ll, lp, lq, (const double*)ctx->d_ptab, ps,
-                       rho_ptr, step, block_counts);
+    const PcnScalars ps = pcn_scalars(pd);
+    ASMC_LAUNCH(ctx, st, pcn_reg_label(MODE), kern, dim3(grid), dim3(wpb * 64), lds_bytes, st, n, x, ll, lp, lq,
+                (const double*)ctx->d_ptab, ps, rho_ptr, step, block_counts);
     ASMC_LAUNCH_CHECK();
     return ASMC_OK;
 }
@@ -1609,21 +1270,7 @@ static int launch_pcn_reg_flow(asmc_ctx* ctx, int64_t n, T* y, T* x_prop, double
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         attr_set = true;
     }
-    PcnScalars ps;
-    ps.beta = pd.beta;
-    ps.nu = pd.nu;
-    ps.gam = pd.gam;
-    ps.ys = pd.ys;
-    ps.n_pad = pd.n_pad;
-    ps.d_real = pd.d;
-    ps.seed = pd.seed;
-    ps.gid0 = pd.gid0;
-    ps.bmtab = pd.bmtab;
-    ps.tile_par = pd.tile_par;
-    ps.d_noise = pd.d_noise;
-    ps.c_ll = pd.ll.C;
-    ps.c_lp = pd.lp.C;
-    ps.c_lq = pd.lq.C;
+    const PcnScalars ps = pcn_scalars(pd);
     ASMC_LAUNCH(ctx, st, (MODE == PCN_FLOW_PROPOSE || MODE == PCN_FLOW_PROPOSE_S || MODE == PCN_FLOW_PROPOSE_SX || MODE >= PCN_FLOW_PROPOSE_SXT_LOGIT) ? "k_pcn_flow_propose" : "k_pcn_flow_accept", kern, dim3((int)grid64),
                 dim3(wpb * 64), lds_bytes, st, n, y, x_prop, ll, lp, lq, ll_new, lp_new, lq_new, (const double*)ctx->d_ptab, ps,
                 rho_ptr, step, block_counts);
@@ -1740,12 +1387,6 @@ static int launch_pcn_step(asmc_ctx* ctx, int64_t n, T* x, double* ll, double* l
     return ASMC_OK;
 }
 
-static int check_mixture(const asmc_mixture& m) {
-    ASMC_REQUIRE(m.n_components >= 1 && m.n_components <= ASMC_MAX_COMPONENTS, "mixture: bad component count");
-    ASMC_REQUIRE(m.logw_dev && m.mu_dev && m.prec_dev, "mixture: null device pointer");
-    return ASMC_OK;
-}
-
 // ---- any d <= 128 on the fast kernels: zero-padding to the next supported width ------------------------------------------
 // The register-resident kernels exist for d in {4, 8, 16, 32}, the matrix-core kernels for d in {64, 128}; every other d used
 // to fall to the generic LDS kernel (6-9x slower).  A d-dimensional problem is the same as the D-dimensional one with
@@ -1753,12 +1394,6 @@ static int check_mixture(const asmc_mixture& m) {
 // noise on the padded coordinates (PcnDev.d_noise: y' = 0 there, |y|^2 and the Student-t dimension stay d's) - the real
 // coordinates see exactly the arithmetic of the unpadded specification (same noise words: they are keyed by coordinate).
 // Cost: two copy passes over the rows per call (pad, un-pad) and N x D x s bytes of scratch, grown on demand.
-static int pcn_pad_dim(int d) {
-    const int widths[] = {4, 8, 16, 32, 64, 128};
-    for (int D : widths)
-        if (d <= D) return D;
-    return 0;
-}
 template <typename T>
 __global__ __launch_bounds__(ASMC_BLOCK) void k_pad_rows(int64_t n, int d, int D, const T* __restrict__ x, T* __restrict__ xp) {
     const int64_t total = n * D, stride = (int64_t)gridDim.x * ASMC_BLOCK;
@@ -1801,612 +1436,102 @@ __global__ __launch_bounds__(256) void k_pad_tables(int d, int D, PcnDev p, doub
     }
 }
 
-extern "C" {
-
-int asmc_gaussian_draw(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const double* mu, const double* sigma,
-                       uint64_t seed, uint64_t gid0, uint32_t draw_id, void* x_out, double* lq_out,
-                       asmc_stream stream) {
-    ASMC_REQUIRE(ctx && mu && sigma && x_out, "null pointer");
-    ASMC_REQUIRE(n > 0 && d > 0 && d <= ASMC_MAX_DIMS, "bad sizes");
-    ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    hipStream_t st = as_stream(stream);
-    const int grid = grid_for(n * ((d + 3) / 4), ASMC_BLOCK * 2, ASMC_MAX_BLOCKS * 2);
-    const int grid2 = grid_for(n, ASMC_BLOCK, ASMC_MAX_BLOCKS * 2);
-    if (x_dtype == ASMC_F64) {
-        ASMC_LAUNCH(ctx, st, "k_gaussian_draw<double>", k_gaussian_draw<double>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, mu, sigma,
-                           (unsigned long long)seed, (unsigned long long)gid0, draw_id, (double*)x_out, (const double*)ctx->d_bmtab);
-        ASMC_LAUNCH_CHECK();
-        if (lq_out) ASMC_LAUNCH(ctx, st, "k_gaussian_logq<double>", k_gaussian_logq<double>, dim3(grid2), dim3(ASMC_BLOCK), 0, st, n, d, mu, sigma, (const double*)x_out, lq_out);
-    } else {
-        ASMC_LAUNCH(ctx, st, "k_gaussian_draw<float>", k_gaussian_draw<float>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, mu, sigma,
-                           (unsigned long long)seed, (unsigned long long)gid0, draw_id, (float*)x_out, (const double*)ctx->d_bmtab);
-        ASMC_LAUNCH_CHECK();
-        if (lq_out) ASMC_LAUNCH(ctx, st, "k_gaussian_logq<float>", k_gaussian_logq<float>, dim3(grid2), dim3(ASMC_BLOCK), 0, st, n, d, mu, sigma, (const float*)x_out, lq_out);
-    }
-    ASMC_LAUNCH_CHECK();
-    return ASMC_OK;
-}
-
-static int mixture_logpdf_impl(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, const asmc_mixture* density,
-                               double* out, const double* premap, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && density && out, "null pointer");
-    ASMC_REQUIRE(n > 0 && d > 0 && d <= ASMC_MAX_DIMS, "bad sizes");
-    ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    int rc = check_mixture(*density);
-    if (rc) return rc;
-    hipStream_t st = as_stream(stream);
-    const int elem = x_dtype == ASMC_F64 ? 8 : 4;
-    const int rowbytes = d * elem;
-    size_t lds_bytes = 0;
-    const int wpb = waves_for_lds((size_t)64 * lds_row_stride(rowbytes), &lds_bytes);
-    const int64_t n_tiles = (n + 63) / 64;
-    int cap = ctx->num_cu * 4;
-    if (cap > ASMC_MAX_BLOCKS) cap = ASMC_MAX_BLOCKS;
-    const int grid = grid_for(n_tiles, wpb, cap);
-    const int vec = pick_vec(rowbytes, x, x);
-    const MixDev m = to_dev(*density);
-    {
-        const int pieces = rowbytes / 16;
-        if (rowbytes % 16 == 0 && ((uintptr_t)x % 16) == 0 && pieces >= 1 && pieces <= 64 && (pieces & (pieces - 1)) == 0 &&
-            m.C <= 4 && !getenv("ASMC_MIXTURE_TILED")) {
-            int lg = 0;
-            while ((1 << lg) < pieces) lg++;
-            const int g = grid_for(n * pieces, ASMC_BLOCK, ctx->num_cu * 32);
-            if (x_dtype == ASMC_F64) {
-                if (m.C == 1)
-                    ASMC_LAUNCH(ctx, st, "k_mixture_logpdf", (k_mixture_flat<double, 1>), dim3(g), dim3(ASMC_BLOCK), 0, st, n, d, lg,
-                                (const uint4*)x, m, out, premap);
-                else
-                    ASMC_LAUNCH(ctx, st, "k_mixture_logpdf", (k_mixture_flat<double, 4>), dim3(g), dim3(ASMC_BLOCK), 0, st, n, d, lg,
-                                (const uint4*)x, m, out, premap);
-            } else {
-                if (m.C == 1)
-                    ASMC_LAUNCH(ctx, st, "k_mixture_logpdf", (k_mixture_flat<float, 1>), dim3(g), dim3(ASMC_BLOCK), 0, st, n, d, lg,
-                                (const uint4*)x, m, out, premap);
-                else
-                    ASMC_LAUNCH(ctx, st, "k_mixture_logpdf", (k_mixture_flat<float, 4>), dim3(g), dim3(ASMC_BLOCK), 0, st, n, d, lg,
-                                (const uint4*)x, m, out, premap);
-            }
-            ASMC_LAUNCH_CHECK();
-            return ASMC_OK;
-        }
-    }
-    if (premap) {
-        asmc_set_error("asmc_mixture_logpdf_premap: rows must be a power-of-two number (<= 64) of 16-byte pieces, <= 4 components");
-        return ASMC_ERR_UNSUPPORTED;
-    }
-    auto launch = [&](auto kern, auto xp) {
-        if (lds_bytes > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        ASMC_LAUNCH(ctx, st, "k_mixture_logpdf", kern, dim3(grid), dim3(wpb * 64), lds_bytes, st, n, d, xp, m, out, wpb);
-    };
-    if (x_dtype == ASMC_F64) {
-        const double* xp = (const double*)x;
-        if (vec == 16) launch(k_mixture_logpdf<double, 16>, xp);
-        else launch(k_mixture_logpdf<double, 8>, xp);
-    } else {
-        const float* xp = (const float*)x;
-        if (vec == 16) launch(k_mixture_logpdf<float, 16>, xp);
-        else if (vec == 8) launch(k_mixture_logpdf<float, 8>, xp);
-        else launch(k_mixture_logpdf<float, 4>, xp);
-    }
-    ASMC_LAUNCH_CHECK();
-    return ASMC_OK;
-}
-
-int asmc_mixture_logpdf(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, const asmc_mixture* density,
-                        double* out, asmc_stream stream) {
-    return mixture_logpdf_impl(ctx, n, d, x_dtype, x, density, out, nullptr, stream);
-}
-
-int asmc_mixture_logpdf_premap(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, const double* premap_dev,
-                               const asmc_mixture* density, double* out, asmc_stream stream) {
-    ASMC_REQUIRE(premap_dev != nullptr, "null premap");
-    return mixture_logpdf_impl(ctx, n, d, x_dtype, x, density, out, premap_dev, stream);
-}
-
-int asmc_colsum(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, double* sum_host, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && sum_host, "null pointer");
-    ASMC_REQUIRE(n > 0 && d > 0 && d <= ctx->d_max && d <= ASMC_BLOCK, "bad sizes");
-    ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    hipStream_t st = as_stream(stream);
-    int grid = grid_for(n, (ASMC_BLOCK / d) * 16, ctx->gram_blocks);
-    if (x_dtype == ASMC_F64)
-        ASMC_LAUNCH(ctx, st, "k_colsum<double>", k_colsum<double>, dim3(grid), dim3(ASMC_BLOCK), ASMC_BLOCK * sizeof(double), st, n, d, (const double*)x, ctx->d_gram);
-    else
-        ASMC_LAUNCH(ctx, st, "k_colsum<float>", k_colsum<float>, dim3(grid), dim3(ASMC_BLOCK), ASMC_BLOCK * sizeof(double), st, n, d, (const float*)x, ctx->d_gram);
-    ASMC_LAUNCH_CHECK();
-    ASMC_LAUNCH(ctx, st, "k_reduce_columns", k_reduce_columns, dim3(d), dim3(64), 0, st, grid, d, (const double*)ctx->d_gram, ctx->d_small);
-    ASMC_LAUNCH_CHECK();
-    ASMC_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_small, sizeof(double) * d, hipMemcpyDeviceToHost, st));
-    ASMC_HIP(hipStreamSynchronize(st));
-    memcpy(sum_host, ctx->h_pinned, sizeof(double) * d);
-    return ASMC_OK;
-}
-
-__global__ void k_center_from_sum(int d, const double* __restrict__ sum, double n, double* __restrict__ center) {
-    const int j = threadIdx.x;
-    if (j < d) center[j] = sum[j] / n;
-}
-
-// The reference Gaussian of a mutation from the population moments, on the device (smc/minipcn.py:75-84: mean and
-// covariance of the particles; this repository's pCN specification whitens with the Cholesky factor): what the host did with
-// numpy between two temperatures - cov = G / (n - 1), symmetrised; L = chol(cov + jitter * mean(diag) * I) with the jitter
-// ladder 0, 1e-12, 1e-10, ... of twelve tries (denom = n - 1); Linv = L^-1 - in ONE block behind the Gram kernel, so the mutation's kernels
-// follow without a host round trip (fetch, LAPACK, upload: ~0.2 ms of idle GPU per temperature).
-// out = [mu (seg) | L (d x d, zeros above the diagonal) | pad to seg x d | Linv (d x d)], seg = 32 ceil(d / 32) doubles;
-// status[0] = jitter tries used (0: none), -1: not factorable / not finite.
-#define REF_THREADS 256
-// Also the factorisation inside the device-side EM of the Student-t reference (asmc_student_fit): `sum` == NULL leaves the mean
-// alone, `tab` (mu | Linv's lower triangle packed by rows) is what k_student_estep stages, `em` / `it`: the EM's state record -
-// iterations behind the one that converged are skipped, a failed factorisation is recorded there.
-__global__ __launch_bounds__(1024) void k_ref_factor(int d, const double* __restrict__ sum, const double* __restrict__ gram,
-                                                           double n_mean, double denom, double* __restrict__ out,
-                                                           double* __restrict__ status, double* __restrict__ tab,
-                                                           double* __restrict__ em, int it) {
-    extern __shared__ __align__(16) double s_a[];  // [d][d + 1]
-    __shared__ double s_diag[128], s_rdiag[128];
-    __shared__ double s_scale;
-    if (em && (double)it > em[2]) return;  // (uniform: every thread reads the same cell)
-    const int tid = threadIdx.x, ld = d + 1, seg = (d + 31) / 32 * 32;
-    const int NT = (int)blockDim.x;  // (one wave for d <= 32 - free barriers - was measured: 63 us against 40 with four)
-    double* o_mu = out;
-    double* o_L = out + seg;
-    double* o_Li = out + seg + (size_t)seg * d;
-    if (sum)
-        for (int j = tid; j < d; j += NT) {
-            const double mj = sum[j] / n_mean;
-            if (out) o_mu[j] = mj;
-            if (tab) tab[j] = mj;
-        }
-    const double inv_denom = 1.0 / denom;
-    int tries = -1;
-    double jitter = 0.0;
-    for (int attempt = 0; attempt < 12; attempt++) {
-        __syncthreads();
-        for (int e = tid; e < d * d; e += NT) {
-            const int i = e / d, j = e - i * d;
-            s_a[i * ld + j] = 0.5 * (gram[(size_t)i * d + j] * inv_denom + gram[(size_t)j * d + i] * inv_denom);
-        }
-        __syncthreads();
-        if (attempt == 0) {
-            if (tid == 0) {
-                double t = 0.0;
-                for (int j = 0; j < d; j++) t += s_a[j * ld + j];
-                t /= (double)d;
-                s_scale = (t > 0.0 && t < INFINITY) ? t : 1.0;
-            }
-        } else {
-            for (int j = tid; j < d; j += NT) s_a[j * ld + j] += jitter * s_scale;
-        }
-        // right-looking Cholesky with ONE barrier per column: the trailing block takes A[i][k] -= A[i][j] A[k][j] / A[j][j]
-        // (kept symmetric: both halves are updated); column j itself is left unscaled - it is not read again - and becomes
-        // L[i][j] = A[i][j] / sqrt(A[j][j]) in the pass behind the loop
-        bool ok = true;
-        for (int j = 0; j < d; j++) {
-            __syncthreads();
-            const double p = s_a[j * ld + j];  // the same value in every thread: the test below is uniform
-            if (!(p > 0.0 && p < INFINITY)) {
-                ok = false;
-                break;
-            }
-            double rp = __builtin_amdgcn_rcp(p);  // hardware reciprocal + two Newton steps: the division's chain is half of a column's latency
-            rp = fma(fma(-p, rp, 1.0), rp, rp);
-            rp = fma(fma(-p, rp, 1.0), rp, rp);
-            // threads as a (NT / 32) x 32 patch walking the trailing block: no integer division per element
-            for (int i = j + 1 + (tid >> 5); i < d; i += NT >> 5) {
-                const double li = s_a[i * ld + j] * rp;
-                for (int k = j + 1 + (tid & 31); k < d; k += 32) s_a[i * ld + k] = fma(-li, s_a[k * ld + j], s_a[i * ld + k]);
-            }
-        }
-        if (ok) {
-            tries = attempt;
-            break;
-        }
-        jitter = jitter == 0.0 ? 1e-12 : jitter * 100.0;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        if (status) status[0] = (double)tries;
-        if (em && tries < 0) em[3] = -1.0;
-    }
-    if (tries < 0) {
-        // no factor: poison (L, Linv) so that a mutation that runs before the host has looked at the status cannot use the
-        // factors an earlier fit left in this slot - NaN proposals are rejected and counted, never silently accepted
-        if (out)
-            for (int e = tid; e < d * d; e += NT) o_L[e] = __builtin_nan(""), o_Li[e] = __builtin_nan("");
-        if (tab)
-            for (int e = tid; e < d * (d + 1) / 2; e += NT) tab[d + e] = __builtin_nan("");
-        return;
-    }
-    for (int j = tid; j < d; j += NT) {
-        const double sd = sqrt(s_a[j * ld + j]);
-        s_diag[j] = sd, s_rdiag[j] = 1.0 / sd;
-    }
-    __syncthreads();
-    for (int e = tid; e < d * d; e += NT) {
-        const int i = e / d, j = e - i * d;
-        double v = 0.0;
-        if (j < i) v = s_a[i * ld + j] * s_rdiag[j];
-        if (j == i) v = s_diag[j];
-        if (out) o_L[e] = v;
-        if (j < i) s_a[i * ld + j] = v;  // (the strict lower triangle: no other thread touches it in this pass)
-    }
-    __syncthreads();
-    // Linv by forward substitution, every column at once and without a block barrier: a group of G lanes of one wave solves
-    // L x = e_c for column c - the lanes split the dot product of a row (a single lane's chain of d^2 / 2 dependent LDS reads
-    // was 30 of the kernel's 40 us at d = 32 and 520 us at d = 128) - and keeps x_i (i > c) in the FREE upper triangle, at
-    // A[c][i], its own row; L is only read.  LDS operations of a wave complete in order: the lanes of a group see x_i
-    // as soon as the instruction that wrote it has issued.
-    {
-        const int per = NT / d;
-        const int G = per >= 8 ? 8 : per >= 4 ? 4 : per >= 2 ? 2 : 1;
-        const int c = tid / G, q = tid % G;
-        if (c < d) {
-            const double xc = s_rdiag[c];
-            for (int i = c + 1; i < d; i++) {
-                double acc = q == 0 ? s_a[i * ld + c] * xc : 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-                int k = c + 1 + q;
-                for (; k + 3 * G < i; k += 4 * G) {  // four independent chains: the LDS reads of a row pipeline
-                    acc = fma(s_a[i * ld + k], s_a[c * ld + k], acc);
-                    acc1 = fma(s_a[i * ld + k + G], s_a[c * ld + k + G], acc1);
-                    acc2 = fma(s_a[i * ld + k + 2 * G], s_a[c * ld + k + 2 * G], acc2);
-                    acc3 = fma(s_a[i * ld + k + 3 * G], s_a[c * ld + k + 3 * G], acc3);
-                }
-                for (; k < i; k += G) acc = fma(s_a[i * ld + k], s_a[c * ld + k], acc);
-                acc = (acc + acc1) + (acc2 + acc3);
-                for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-                if (q == 0) s_a[c * ld + i] = -acc * s_rdiag[i];
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-    }
-    __syncthreads();
-    for (int e = tid; e < d * d; e += NT) {
-        const int i = e / d, j = e - i * d;
-        const double v = j < i ? s_a[j * ld + i] : j == i ? s_rdiag[i] : 0.0;
-        if (out) o_Li[e] = v;
-        if (tab && j <= i) tab[d + i * (i + 1) / 2 + j] = v;
-    }
-}
-
-// Column sums and the Gram matrix centred on sum / n_mean in ONE enqueue and one synchronisation (the reference fit of a
-// temperature boundary: the centre never visits the host; same division, same kernels, same bits as asmc_colsum -> host
-// division -> asmc_centered_gram).  _enqueue leaves both results on their way to pinned memory, _fetch waits for the stream
-// and hands them out: a caller with other work on the stream (the importance step's chain) pays one synchronisation for all.
-int asmc_mean_gram_enqueue(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, int64_t n_mean, int across_flags,
-                           asmc_stream stream) {
-    const int across_ranks = across_flags & ASMC_GRAM_ACROSS_RANKS;
-    ASMC_REQUIRE(ctx && x, "null pointer");
-    ASMC_REQUIRE(n > 0 && n_mean > 0 && d > 0 && d <= ctx->d_max && d <= 128, "bad sizes (gram supports d <= 128)");
-    ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    ASMC_REQUIRE(asmc_gram_mm_supported(d, x) && d <= ASMC_BLOCK && !getenv("ASMC_GRAM_GENERIC"),
-                 "shape without the device-side path (asmc_mean_gram falls back to the two calls; across_ranks: merge on the host)");
-    typedef int (*allreduce_fn)(const void*, void*, size_t, int, int, void*, hipStream_t);
-    const allreduce_fn allreduce = reinterpret_cast<allreduce_fn>(ctx->rccl_allreduce);
-    const int nccl_f64 = 8, nccl_sum = 0;  // rccl.h: ncclFloat64, ncclSum
-    ASMC_REQUIRE(!across_ranks || (allreduce && ctx->rccl_comm), "across_ranks needs asmc_set_rccl");
-    hipStream_t st = as_stream(stream);
-    int grid = grid_for(n, (ASMC_BLOCK / d) * 16, ctx->gram_blocks);
-    // rows that asmc_gather has just written AND that the caller vouches for (ASMC_GRAM_FROM_GATHER: nothing has rewritten them
-    // since - the library cannot see a caller's own kernels): their column-sum partials came with the gather, no pass over the rows
-    const bool from_gather = (across_flags & ASMC_GRAM_FROM_GATHER) && ctx->cs_n == n && ctx->cs_x == x && ctx->cs_d == d &&
-                             x_dtype == ASMC_F64;
-    if (from_gather)
-        grid = ctx->cs_grid;
-    else if (x_dtype == ASMC_F64)
-        ASMC_LAUNCH(ctx, st, "k_colsum<double>", k_colsum<double>, dim3(grid), dim3(ASMC_BLOCK), ASMC_BLOCK * sizeof(double), st, n, d, (const double*)x, ctx->d_gram);
-    else
-        ASMC_LAUNCH(ctx, st, "k_colsum<float>", k_colsum<float>, dim3(grid), dim3(ASMC_BLOCK), ASMC_BLOCK * sizeof(double), st, n, d, (const float*)x, ctx->d_gram);
-    ASMC_LAUNCH_CHECK();
-    // the results stay on the device in ctx->d_ref = {sums [128], Gram} (d_small / d_partials are every call's scratch):
-    // asmc_reference_factor reads them there, asmc_mean_gram_fetch copies them out when a caller wants them on the host.  The
-    // reductions write them there themselves, the all-reduces of a sharded run work on them in place, and the Gram kernel forms
-    // the centre sum / n_mean itself: no launch sits between the passes and the collectives.
-    ASMC_LAUNCH(ctx, st, "k_reduce_columns", k_reduce_columns, dim3(d), dim3(from_gather ? 256 : 64), 0, st, grid, d,
-                (const double*)ctx->d_gram, ctx->d_small, ctx->d_ref, (double*)nullptr, (double)n_mean);
-    ASMC_LAUNCH_CHECK();
-    if (across_ranks && allreduce(ctx->d_ref, ctx->d_ref, (size_t)d, nccl_f64, nccl_sum, ctx->rccl_comm, st) != 0) {
-        asmc_set_error("asmc_mean_gram: ncclAllReduce failed");
-        return ASMC_ERR_ARG;
-    }
-    int ggrid = 0;
-    int rc = asmc_gram_mm_launch(ctx, n, d, x_dtype, x, ctx->d_ref, &ggrid, st, ctx->d_ref + 128, (double)n_mean);
-    if (rc) return rc;
-    if (across_ranks && allreduce(ctx->d_ref + 128, ctx->d_ref + 128, (size_t)d * d, nccl_f64, nccl_sum, ctx->rccl_comm, st) != 0) {
-        asmc_set_error("asmc_mean_gram: ncclAllReduce failed");
-        return ASMC_ERR_ARG;
-    }
-    ctx->gram_pending_d = d;
-    return ASMC_OK;
-}
-
-int asmc_mean_gram_fetch(asmc_ctx* ctx, int d, double* sum_host, double* gram_host, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && sum_host && gram_host, "null pointer");
-    ASMC_REQUIRE(ctx->gram_pending_d == d && d > 0, "no asmc_mean_gram_enqueue of this d is pending");
-    ASMC_HIP(hipMemcpyAsync(ctx->h_gram, ctx->d_ref, sizeof(double) * (128 + (size_t)d * d), hipMemcpyDeviceToHost, as_stream(stream)));
-    ASMC_HIP(hipStreamSynchronize(as_stream(stream)));
-    memcpy(sum_host, ctx->h_gram, sizeof(double) * d);
-    memcpy(gram_host, ctx->h_gram + 128, sizeof(double) * d * d);
-    ctx->gram_pending_d = 0;
-    return ASMC_OK;
-}
-
-}  // extern "C"
-// Every factorisation request reads its status back into a pinned cell OF ITS OWN (a ring indexed by a generation counter): the
-// host writes the "not yet known" sentinel into a cell that no copy still in flight targets - an earlier request's late copy
-// lands in its own cell and cannot be mistaken for this request's status.  (The ring is deeper than the requests a caller can
-// have in flight between two synchronisations: one per temperature.)
-#define REF_STATUS_CELL0 8010
-#define REF_STATUS_CELLS 16
-static int ref_status_request(asmc_ctx* ctx, const double* d_status, hipStream_t st) {
-    ctx->ref_status_gen++;
-    double* cell = ctx->h_pinned + REF_STATUS_CELL0 + ctx->ref_status_gen % REF_STATUS_CELLS;
-    *cell = -2.0;
-    ASMC_HIP(hipMemcpyAsync(cell, d_status, sizeof(double), hipMemcpyDeviceToHost, st));
-    return ASMC_OK;
-}
-
-int asmc_ref_factor_launch(asmc_ctx* ctx, int d, const double* sum, const double* gram, double n_mean, double denom, double* out,
-                           double* status, double* tab, double* em, int it, hipStream_t st) {
-    const size_t lds = sizeof(double) * (size_t)d * (d + 1);
-    static size_t attr_lds_dev[ASMC_MAX_DEVICES] = {0}; size_t& attr_lds = attr_lds_dev[asmc_dev_slot(ctx)];
-    if (lds > 64 * 1024 && lds > attr_lds) {
-        ASMC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ref_factor), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
-    // d <= 32 is bound by the per-column latency whatever the block (38-41 us from 256 to 1024 threads); d = 128 by the trailing
-    // updates: 683 us with 256 threads, 516 with 1024
-    // (ASMC_REF_THREADS is a debugging knob for that measurement: a block smaller than d threads is not supported by the kernel -
-    // its last passes give every column a thread - and no test covers the knob)
-    static const int ref_env = getenv("ASMC_REF_THREADS") ? atoi(getenv("ASMC_REF_THREADS")) : 0;
-    const int ref_threads = ref_env > 0 ? ref_env : (d <= 32 ? REF_THREADS : 1024);
-    ASMC_LAUNCH(ctx, st, "k_ref_factor", k_ref_factor, dim3(1), dim3(ref_threads), lds, st, d, sum, gram, n_mean, denom, out,
-                status, tab, em, it);
-    ASMC_LAUNCH_CHECK();
-    return ASMC_OK;
-}
-extern "C" {
-
-// (mu, L, Linv) of the reference Gaussian from the moments of the pending asmc_mean_gram_enqueue (consumed: no fetch
-// follows) or, with sum_host / gram_host, from moments the caller merged on the host (uploaded first): k_ref_factor on the
-// stream.  The status lands in pinned memory behind it; asmc_reference_factor_status reads it after the caller's next
-// synchronisation of the stream.
-int asmc_reference_factor(asmc_ctx* ctx, int d, int64_t n_mean, int64_t n_cov, const double* sum_host, const double* gram_host,
-                          double* out_dev, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && out_dev, "null pointer");
-    ASMC_REQUIRE(d > 0 && d <= 128 && n_mean > 0 && n_cov > 0, "bad sizes (d <= 128)");
-    ASMC_REQUIRE((sum_host == nullptr) == (gram_host == nullptr), "sum_host and gram_host come together");
-    hipStream_t st = as_stream(stream);
-    if (gram_host) {
-        ASMC_REQUIRE(ctx->gram_pending_d == 0, "an asmc_mean_gram_enqueue is pending: its results would be overwritten");
-        ASMC_HIP(hipStreamSynchronize(st));  // (the pinned staging may still feed an earlier copy)
-        memcpy(ctx->h_gram, sum_host, sizeof(double) * d);
-        memcpy(ctx->h_gram + 128, gram_host, sizeof(double) * d * d);
-        ASMC_HIP(hipMemcpyAsync(ctx->d_ref, ctx->h_gram, sizeof(double) * (128 + (size_t)d * d), hipMemcpyHostToDevice, st));
-    } else {
-        ASMC_REQUIRE(ctx->gram_pending_d == d, "no asmc_mean_gram_enqueue of this d is pending");
-        ctx->gram_pending_d = 0;
-    }
-    double* d_status = ctx->d_small + 2300;
-    const int rc = asmc_ref_factor_launch(ctx, d, ctx->d_ref, ctx->d_ref + 128, (double)n_mean, (double)(n_cov - 1 > 1 ? n_cov - 1 : 1),
-                                          out_dev, d_status, nullptr, nullptr, 0, st);
-    if (rc) return rc;
-    return ref_status_request(ctx, d_status, st);
-}
-
-// The sharded form of the same fit without a host round trip: column sums and the centred Gram matrix into the CALLER's device
-// buffers (the caller sums each over the ranks with its own stream-ordered all-reduce), then the factorisation from them.
-__global__ __launch_bounds__(256) void k_copy_doubles(int n, const double* __restrict__ src, double* __restrict__ dst) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < n) dst[e] = src[e];
-}
-
-int asmc_colsum_dev(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, int from_gather_flag, double* sum_dev,
-                    asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && sum_dev, "null pointer");
-    ASMC_REQUIRE(n > 0 && d > 0 && d <= ctx->d_max && d <= ASMC_BLOCK, "bad sizes");
-    ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    hipStream_t st = as_stream(stream);
-    int grid = grid_for(n, (ASMC_BLOCK / d) * 16, ctx->gram_blocks);
-    const bool from_gather = from_gather_flag && ctx->cs_n == n && ctx->cs_x == x && ctx->cs_d == d && x_dtype == ASMC_F64;  // (see asmc_mean_gram_enqueue)
-    if (from_gather)
-        grid = ctx->cs_grid;
-    else if (x_dtype == ASMC_F64)
-        ASMC_LAUNCH(ctx, st, "k_colsum<double>", k_colsum<double>, dim3(grid), dim3(ASMC_BLOCK), ASMC_BLOCK * sizeof(double), st, n, d, (const double*)x, ctx->d_gram);
-    else
-        ASMC_LAUNCH(ctx, st, "k_colsum<float>", k_colsum<float>, dim3(grid), dim3(ASMC_BLOCK), ASMC_BLOCK * sizeof(double), st, n, d, (const float*)x, ctx->d_gram);
-    ASMC_LAUNCH_CHECK();
-    ASMC_LAUNCH(ctx, st, "k_reduce_columns", k_reduce_columns, dim3(d), dim3(from_gather ? 256 : 64), 0, st, grid, d, (const double*)ctx->d_gram, sum_dev);
-    ASMC_LAUNCH_CHECK();
-    return ASMC_OK;
-}
-
-int asmc_centered_gram_dev(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, const double* sum_dev, int64_t n_mean,
-                           double* gram_dev, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && sum_dev && gram_dev, "null pointer");
-    ASMC_REQUIRE(n > 0 && n_mean > 0 && d > 0 && d <= ctx->d_max && d <= 128, "bad sizes (gram supports d <= 128)");
-    ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    if (!asmc_gram_mm_supported(d, x) || getenv("ASMC_GRAM_GENERIC")) {
-        asmc_set_error("asmc_centered_gram_dev: shape without the matrix-core Gram kernel (d in {32, 64, 128}, 16-byte aligned rows)");
-        return ASMC_ERR_UNSUPPORTED;
-    }
-    hipStream_t st = as_stream(stream);
-    double* d_center = ctx->d_small + 2048;
-    ASMC_LAUNCH(ctx, st, "k_center_from_sum", k_center_from_sum, dim3(1), dim3(128), 0, st, d, sum_dev, (double)n_mean, d_center);
-    ASMC_LAUNCH_CHECK();
-    int ggrid = 0;
-    const int rc = asmc_gram_mm_launch(ctx, n, d, x_dtype, x, d_center, &ggrid, st, nullptr, 0.0);
-    if (rc) return rc;
-    ASMC_LAUNCH(ctx, st, "k_copy_doubles", k_copy_doubles, dim3((d * d + 255) / 256), dim3(256), 0, st, d * d, (const double*)ctx->d_partials,
-                gram_dev);
-    ASMC_LAUNCH_CHECK();
-    return ASMC_OK;
-}
-
-int asmc_reference_factor_dev(asmc_ctx* ctx, int d, int64_t n_mean, int64_t n_cov, const double* sum_dev, const double* gram_dev,
-                              double* out_dev, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && sum_dev && gram_dev && out_dev, "null pointer");
-    ASMC_REQUIRE(d > 0 && d <= 128 && n_mean > 0 && n_cov > 0, "bad sizes (d <= 128)");
-    hipStream_t st = as_stream(stream);
-    double* d_status = ctx->d_small + 2300;
-    const int rc = asmc_ref_factor_launch(ctx, d, sum_dev, gram_dev, (double)n_mean, (double)(n_cov - 1 > 1 ? n_cov - 1 : 1), out_dev,
-                                          d_status, nullptr, nullptr, 0, st);
-    if (rc) return rc;
-    return ref_status_request(ctx, d_status, st);
-}
-
-int asmc_reference_factor_status(asmc_ctx* ctx, int* status_host) {
-    ASMC_REQUIRE(ctx && status_host, "null pointer");
-    *status_host = (int)ctx->h_pinned[REF_STATUS_CELL0 + ctx->ref_status_gen % REF_STATUS_CELLS];  // -2: the stream has not been synchronised since asmc_reference_factor
-    return ASMC_OK;
-}
-
-// the request a caller has just made, and the status of one particular request: a mutation asks about the factorisation
-// that served IT - the next temperature's may already be on the stream behind it (asmc_reference_factor_status reads the latest
-// request's cell: -2 until that one has run)
-int64_t asmc_reference_factor_generation(asmc_ctx* ctx) { return ctx ? (int64_t)ctx->ref_status_gen : -1; }
-int asmc_reference_factor_status_of(asmc_ctx* ctx, int64_t generation, int* status_host) {
-    ASMC_REQUIRE(ctx && status_host, "null pointer");
-    ASMC_REQUIRE(generation > 0 && (uint64_t)generation <= ctx->ref_status_gen &&
-                     ctx->ref_status_gen - (uint64_t)generation < REF_STATUS_CELLS,
-                 "no such factorisation request (or more than 15 requests ago)");
-    *status_host = (int)ctx->h_pinned[REF_STATUS_CELL0 + (unsigned)generation % REF_STATUS_CELLS];
-    return ASMC_OK;
-}
-
-int asmc_mean_gram(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, int64_t n_mean, int across_ranks,
-                   double* sum_host, double* gram_host, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && sum_host && gram_host, "null pointer");
-    ASMC_REQUIRE(n > 0 && n_mean > 0 && d > 0 && d <= ctx->d_max && d <= 128, "bad sizes (gram supports d <= 128)");
-    if (!across_ranks && (!(asmc_gram_mm_supported(d, x) && d <= ASMC_BLOCK) || getenv("ASMC_GRAM_GENERIC"))) {
-        int rc = asmc_colsum(ctx, n, d, x_dtype, x, sum_host, stream);  // shapes without the fp64-MFMA Gram kernel
-        if (rc) return rc;
-        double center[128];
-        for (int j = 0; j < d; j++) center[j] = sum_host[j] / (double)n_mean;
-        return asmc_centered_gram(ctx, n, d, x_dtype, x, center, gram_host, stream);
-    }
-    const int rc = asmc_mean_gram_enqueue(ctx, n, d, x_dtype, x, n_mean, across_ranks, stream);
-    if (rc) return rc;
-    return asmc_mean_gram_fetch(ctx, d, sum_host, gram_host, stream);
-}
-
-int asmc_centered_gram(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, const double* center_host,
-                       double* gram_host, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && center_host && gram_host, "null pointer");
-    ASMC_REQUIRE(n > 0 && d > 0 && d <= ctx->d_max && d <= 128, "bad sizes (gram supports d <= 128)");
-    ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    hipStream_t st = as_stream(stream);
-    ASMC_HIP(hipStreamSynchronize(st));
-    memcpy(ctx->h_pinned + 2048, center_host, sizeof(double) * d);
-    double* d_center = ctx->d_small + 2048;
-    ASMC_HIP(hipMemcpyAsync(d_center, ctx->h_pinned + 2048, sizeof(double) * d, hipMemcpyHostToDevice, st));
-    const size_t elem = x_dtype == ASMC_F64 ? 8 : 4;
-    const int rowbytes = (int)(d * elem);
-    double* d_out = ctx->d_partials;
-    if (asmc_gram_mm_supported(d, x) && ctx->d_max >= d && !getenv("ASMC_GRAM_GENERIC")) {  // fp64 MFMA (asmc_pcn_mm.hip)
-        int grid = 0;
-        int rc = asmc_gram_mm_launch(ctx, n, d, x_dtype, x, d_center, &grid, st, nullptr, 0.0);
-        if (rc) return rc;
-        ASMC_HIP(hipMemcpyAsync(gram_host, d_out, sizeof(double) * d * d, hipMemcpyDeviceToHost, st));
+int pcn_xpad_reserve(asmc_ctx* ctx, size_t need, hipStream_t st, const char* what) {
+    if (need > ctx->xpad_bytes) {
         ASMC_HIP(hipStreamSynchronize(st));
-        return ASMC_OK;
-    }
-    {
-        // any other d <= 128: a zero-padded copy of the rows (centre padded with zeros) through the matrix-core kernel of the next
-        // width >= 32; the d x d corner of its result is the answer (k_gram_rb took 1 ms at d = 48 and 8.5 ms at d = 100 per call)
-        const int D = pcn_pad_dim(d) < 32 ? 32 : pcn_pad_dim(d);
-        if (D > 0 && D != d && D <= (ctx->d_max_pad < 32 ? 32 : ctx->d_max_pad) && !getenv("ASMC_GRAM_GENERIC") && !getenv("ASMC_PCN_NOPAD")) {
-            const size_t need = (size_t)n * D * elem;
-            if (need > ctx->xpad_bytes) {
-                ASMC_HIP(hipStreamSynchronize(st));
-                if (ctx->d_xpad) (void)hipFree(ctx->d_xpad);
-                ctx->d_xpad = nullptr;
-                ctx->xpad_bytes = 0;
-                if (hipMalloc(&ctx->d_xpad, need) != hipSuccess) {
-                    (void)hipGetLastError();
-                    asmc_set_error("centered_gram: no device memory for the zero-padded copy of the rows (%zu bytes)", need);
-                    return ASMC_ERR_NOMEM;
-                }
-                ctx->xpad_bytes = need;
-            }
-            for (int j = d; j < D; j++) ctx->h_pinned[2048 + j] = 0.0;
-            ASMC_HIP(hipMemcpyAsync(d_center, ctx->h_pinned + 2048, sizeof(double) * D, hipMemcpyHostToDevice, st));
-            const int pg = grid_for(n * D, ASMC_BLOCK * 4, ASMC_MAX_BLOCKS * 2);
-            if (elem == 8)
-                ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<double>, dim3(pg), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)x, (double*)ctx->d_xpad);
-            else
-                ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<float>, dim3(pg), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)x, (float*)ctx->d_xpad);
-            ASMC_LAUNCH_CHECK();
-            int grid = 0;
-            int rc = asmc_gram_mm_launch(ctx, n, D, x_dtype, ctx->d_xpad, d_center, &grid, st, nullptr, 0.0);
-            if (rc) return rc;
-            ASMC_HIP(hipMemcpy2DAsync(gram_host, sizeof(double) * d, d_out, sizeof(double) * D, sizeof(double) * d, d,
-                                      hipMemcpyDeviceToHost, st));
-            ASMC_HIP(hipStreamSynchronize(st));
-            return ASMC_OK;
+        if (ctx->d_xpad) (void)hipFree(ctx->d_xpad);
+        ctx->d_xpad = nullptr;
+        ctx->xpad_bytes = 0;
+        if (hipMalloc(&ctx->d_xpad, need) != hipSuccess) {
+            (void)hipGetLastError();
+            asmc_set_error("%s (%zu bytes)", what, need);
+            return ASMC_ERR_NOMEM;
         }
+        ctx->xpad_bytes = need;
     }
-    if (rowbytes % 16 == 0 && ((uintptr_t)x % 16) == 0 && d <= 128) {
-        // register-blocked kernel: BLK = 4 (quadrant 32) for d <= 32, else BLK = 8 (quadrant 64)
-        const int blk = d <= 32 ? 4 : 8;
-        const int Q = 8 * blk;
-        const int nq = (d + Q - 1) / Q;
-        const int dpad = nq * Q;
-        const int wpb = d > 64 ? 2 : ASMC_BLOCK / 64;  // d = 128: two waves per block keep the tiles inside 160 KB of LDS
-        const size_t lds = (size_t)wpb * 64 * lds_row_stride(rowbytes);
-        const size_t lds_red = (size_t)wpb * Q * Q * sizeof(double);
-        const size_t lds_bytes = lds > lds_red ? lds : lds_red;
-        int cap = (int)(((size_t)ctx->gram_blocks * ctx->d_max * ctx->d_max) / ((size_t)dpad * dpad));
-        if (cap > ctx->num_cu * 2) cap = ctx->num_cu * 2;
-        if (cap < 1) {
-            asmc_set_error("centered_gram: ctx d_max=%d too small for d=%d", ctx->d_max, d);
-            return ASMC_ERR_ARG;
-        }
-        const int grid = grid_for((n + 63) / 64, wpb, cap);
-        auto launch = [&](auto kern, auto xp) {
-            if (lds_bytes > 64 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            ASMC_LAUNCH(ctx, st, "k_gram_rb", kern, dim3(grid, nq * nq), dim3(wpb * 64), lds_bytes, st, n, d, xp,
-                        (const double*)d_center, ctx->d_gram, nq);
-        };
-        if (x_dtype == ASMC_F64) {
-            if (blk == 4) launch(k_gram_rb<double, 4>, (const double*)x);
-            else launch(k_gram_rb<double, 8>, (const double*)x);
-        } else {
-            if (blk == 4) launch(k_gram_rb<float, 4>, (const float*)x);
-            else launch(k_gram_rb<float, 8>, (const float*)x);
-        }
-        ASMC_LAUNCH_CHECK();
-        ASMC_LAUNCH(ctx, st, "k_reduce_columns", k_reduce_columns, dim3(dpad * dpad < 1024 ? dpad * dpad : 1024), dim3(64), 0, st, grid,
-                    dpad * dpad, (const double*)ctx->d_gram, d_out);
-        ASMC_LAUNCH_CHECK();
-        // strip the padding while copying back
-        ASMC_HIP(hipMemcpy2DAsync(gram_host, sizeof(double) * d, d_out, sizeof(double) * dpad, sizeof(double) * d, d,
-                                  hipMemcpyDeviceToHost, st));
-        ASMC_HIP(hipStreamSynchronize(st));
-        return ASMC_OK;
-    }
-    ASMC_REQUIRE(d <= 64, "centered_gram: unaligned rows are supported for d <= 64 only");
-    const int grid = grid_for(n, 64 * 8, ctx->gram_blocks);
-    const size_t lds = sizeof(double) * 64 * (d + 1);
-    if (x_dtype == ASMC_F64)
-        ASMC_LAUNCH(ctx, st, "k_gram<double>", k_gram<double>, dim3(grid), dim3(ASMC_BLOCK), lds, st, n, d, (const double*)x, (const double*)d_center, ctx->d_gram);
-    else
-        ASMC_LAUNCH(ctx, st, "k_gram<float>", k_gram<float>, dim3(grid), dim3(ASMC_BLOCK), lds, st, n, d, (const float*)x, (const double*)d_center, ctx->d_gram);
-    ASMC_LAUNCH_CHECK();
-    // d*d <= 4096 doubles: reduce into d_partials, then read back
-    ASMC_LAUNCH(ctx, st, "k_reduce_columns", k_reduce_columns, dim3(d * d < 1024 ? d * d : 1024), dim3(64), 0, st, grid, d * d, (const double*)ctx->d_gram, d_out);
-    ASMC_LAUNCH_CHECK();
-    ASMC_HIP(hipMemcpyAsync(gram_host, d_out, sizeof(double) * d * d, hipMemcpyDeviceToHost, st));
-    ASMC_HIP(hipStreamSynchronize(st));
     return ASMC_OK;
 }
+
+int launch_pad_rows(asmc_ctx* ctx, int64_t n, int d, int D, int x_dtype, const void* src, void* dst, hipStream_t st) {
+    const int grid = grid_for(n * D, ASMC_BLOCK * 4, ASMC_MAX_BLOCKS * 2);
+    if (x_dtype == ASMC_F64)
+        ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<double>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)src, (double*)dst);
+    else
+        ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<float>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)src, (float*)dst);
+    ASMC_LAUNCH_CHECK();
+    return ASMC_OK;
+}
+
+int launch_unpad_rows(asmc_ctx* ctx, int64_t n, int d, int D, int x_dtype, const void* src, void* dst, hipStream_t st) {
+    const int grid = grid_for(n * D, ASMC_BLOCK * 4, ASMC_MAX_BLOCKS * 2);
+    if (x_dtype == ASMC_F64)
+        ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<double>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)src, (double*)dst);
+    else
+        ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<float>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)src, (float*)dst);
+    ASMC_LAUNCH_CHECK();
+    return ASMC_OK;
+}
+
+// The padded problem in ctx->d_xpad: the tables of `src` (a d-dimensional reference and its densities) padded to D at the
+// head, the zero-padded copy of the rows x behind them.  n_mix: how many density tables the caller uses - 3 (ll, lp, lq),
+// 2 (ll, lp: the proposal density is a flow) or 0 (the proposal half of the split path, which also gets a second row buffer
+// xq for x' before the padding is stripped).
+struct PcnPadded {
+    double *mu, *L, *Linv;  // [D], [D, D], [D, D]
+    double* mix;            // 3 x (mu[C_max, D] | prec[C_max, D])
+    void *xp, *xq;
+};
+static int pcn_pad_problem(asmc_ctx* ctx, int64_t n, int d, int D, int x_dtype, const void* x, const PcnDev& src, int n_mix,
+                           hipStream_t st, PcnPadded* out) {
+    const size_t es = x_dtype == ASMC_F64 ? 8 : 4;
+    const size_t tab_doubles = (size_t)D + 2 * (size_t)D * D + (n_mix ? 3 * 2 * (size_t)ASMC_MAX_COMPONENTS * D : 0);
+    const size_t tab_bytes = ((tab_doubles * 8 + 255) / 256) * 256;
+    const size_t row_bytes = (((size_t)n * D * es + 255) / 256) * 256;
+    int rc = n_mix ? pcn_xpad_reserve(ctx, tab_bytes + (size_t)n * D * es, st, "pcn: no device memory for the zero-padded copy of the state")
+                   : pcn_xpad_reserve(ctx, tab_bytes + 2 * row_bytes, st, "pcn: no device memory for the zero-padded copies of a proposal");
+    if (rc) return rc;
+    out->mu = reinterpret_cast<double*>(ctx->d_xpad);
+    out->L = out->mu + D;
+    out->Linv = out->L + (size_t)D * D;
+    out->mix = out->Linv + (size_t)D * D;
+    out->xp = reinterpret_cast<char*>(ctx->d_xpad) + tab_bytes;
+    out->xq = n_mix ? nullptr : reinterpret_cast<char*>(out->xp) + row_bytes;
+    ASMC_LAUNCH(ctx, st, "k_pad_tables", k_pad_tables, dim3(1), dim3(256), 0, st, d, D, src, out->mu);
+    ASMC_LAUNCH_CHECK();
+    return launch_pad_rows(ctx, n, d, D, x_dtype, x, out->xp, st);
+}
+
+// the same from a call's parameters: *p2 = *prm at dimension D, pointing at the padded tables; *xp: the padded rows
+static int pcn_pad_params(asmc_ctx* ctx, int64_t n, const void* x, const asmc_pcn_params* prm, int D, int n_mix, hipStream_t st,
+                          asmc_pcn_params* p2, void** xp) {
+    PcnDev src;
+    memset(&src, 0, sizeof(src));
+    src.mu = prm->mu_dev, src.L = prm->L_dev, src.Linv = prm->Linv_dev;
+    src.ll = to_dev(prm->log_likelihood), src.lp = to_dev(prm->log_prior);
+    src.lq = n_mix == 3 ? to_dev(prm->log_q) : src.lp;  // (two: a placeholder - the proposal density is the flow)
+    PcnPadded pad;
+    const int rc = pcn_pad_problem(ctx, n, prm->d, D, prm->x_dtype, x, src, n_mix, st, &pad);
+    if (rc) return rc;
+    *p2 = *prm;
+    p2->d = D;
+    p2->mu_dev = pad.mu;
+    p2->L_dev = pad.L;
+    p2->Linv_dev = pad.Linv;
+    asmc_mixture* mix[3] = {&p2->log_likelihood, &p2->log_prior, &p2->log_q};
+    for (int k = 0; k < n_mix; k++) {
+        mix[k]->mu_dev = pad.mix + (size_t)k * 2 * ASMC_MAX_COMPONENTS * D;
+        mix[k]->prec_dev = mix[k]->mu_dev + (size_t)ASMC_MAX_COMPONENTS * D;
+    }
+    *xp = pad.xp;
+    return ASMC_OK;
+}
+
+extern "C" {
 
 // coordinate-major scratch for the whitened state of one mutation (grown on demand, kept for the life of the ctx);
 // false when the device has no room for it (callers then stay on the in-place row-major path)
 static bool pcn_ensure_ysoa(asmc_ctx* ctx, int64_t n, int d, int x_dtype, PcnDev& pd, hipStream_t st, bool with_scratch = false) {
-    if (getenv("ASMC_PCN_AOS")) return false;
+    if (pcn_env_aos()) return false;
     const int64_t n_pad = ((n + 63) / 64) * 64;
     const size_t one = (size_t)n_pad * d * (x_dtype == ASMC_F64 ? 8 : 4);
     if (one >= (1ULL << 32)) return false;  // the kernels address the buffer through one 32-bit-offset descriptor
@@ -2511,55 +1636,13 @@ static int pcn_mutate_padded(asmc_ctx* ctx, int64_t n, void* x, double* ll, doub
                              int D, int n_steps, uint32_t step0, double* rho_inout_host, int64_t* n_accept_host,
                              double* rho_hist_host, asmc_stream stream) {
     hipStream_t st = as_stream(stream);
-    const int d = prm->d;
-    const size_t es = prm->x_dtype == ASMC_F64 ? 8 : 4;
-    const size_t tab_doubles = (size_t)D + 2 * (size_t)D * D + 3 * 2 * (size_t)ASMC_MAX_COMPONENTS * D;
-    const size_t tab_bytes = ((tab_doubles * 8 + 255) / 256) * 256;
-    const size_t need = tab_bytes + (size_t)n * D * es;
-    if (need > ctx->xpad_bytes) {
-        ASMC_HIP(hipStreamSynchronize(st));
-        if (ctx->d_xpad) (void)hipFree(ctx->d_xpad);
-        ctx->d_xpad = nullptr;
-        ctx->xpad_bytes = 0;
-        if (hipMalloc(&ctx->d_xpad, need) != hipSuccess) {
-            (void)hipGetLastError();
-            asmc_set_error("pcn: no device memory for the zero-padded copy of the state (%zu bytes)", need);
-            return ASMC_ERR_NOMEM;
-        }
-        ctx->xpad_bytes = need;
-    }
-    double* tab = reinterpret_cast<double*>(ctx->d_xpad);
-    void* xp = reinterpret_cast<char*>(ctx->d_xpad) + tab_bytes;
-    PcnDev src;
-    memset(&src, 0, sizeof(src));
-    src.mu = prm->mu_dev, src.L = prm->L_dev, src.Linv = prm->Linv_dev;
-    src.ll = to_dev(prm->log_likelihood), src.lp = to_dev(prm->log_prior), src.lq = to_dev(prm->log_q);
-    ASMC_LAUNCH(ctx, st, "k_pad_tables", k_pad_tables, dim3(1), dim3(256), 0, st, d, D, src, tab);
-    ASMC_LAUNCH_CHECK();
-    const int grid = grid_for(n * D, ASMC_BLOCK * 4, ASMC_MAX_BLOCKS * 2);
-    if (es == 8)
-        ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<double>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)x, (double*)xp);
-    else
-        ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<float>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)x, (float*)xp);
-    ASMC_LAUNCH_CHECK();
-    asmc_pcn_params p2 = *prm;
-    p2.d = D;
-    p2.mu_dev = tab;
-    p2.L_dev = tab + D;
-    p2.Linv_dev = p2.L_dev + (size_t)D * D;
-    asmc_mixture* mix[3] = {&p2.log_likelihood, &p2.log_prior, &p2.log_q};
-    for (int k = 0; k < 3; k++) {
-        mix[k]->mu_dev = p2.Linv_dev + (size_t)D * D + (size_t)k * 2 * ASMC_MAX_COMPONENTS * D;
-        mix[k]->prec_dev = mix[k]->mu_dev + (size_t)ASMC_MAX_COMPONENTS * D;
-    }
-    int rc = pcn_mutate_impl(ctx, n, xp, ll, lp, lq, &p2, n_steps, step0, rho_inout_host, n_accept_host, rho_hist_host, stream, d);
+    asmc_pcn_params p2;
+    void* xp = nullptr;
+    int rc = pcn_pad_params(ctx, n, x, prm, D, 3, st, &p2, &xp);
     if (rc) return rc;
-    if (es == 8)
-        ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<double>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)xp, (double*)x);
-    else
-        ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<float>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)xp, (float*)x);
-    ASMC_LAUNCH_CHECK();
-    return ASMC_OK;
+    rc = pcn_mutate_impl(ctx, n, xp, ll, lp, lq, &p2, n_steps, step0, rho_inout_host, n_accept_host, rho_hist_host, stream, prm->d);
+    if (rc) return rc;
+    return launch_unpad_rows(ctx, n, prm->d, D, prm->x_dtype, xp, x, st);
 }
 
 extern "C" {
@@ -2571,7 +1654,7 @@ int asmc_pcn_mutate(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, d
     ASMC_REQUIRE(prm->d > 0 && prm->d <= ASMC_MAX_DIMS, "bad d");
     const int D = pcn_pad_dim(prm->d);
     const bool fast_as_is = prm->d == D;
-    if (!fast_as_is && D > 0 && D <= ctx->d_max_pad && !getenv("ASMC_PCN_GENERIC") && !getenv("ASMC_PCN_NOPAD")) {
+    if (!fast_as_is && D > 0 && D <= ctx->d_max_pad && !pcn_env_generic() && !pcn_env_nopad()) {
         ASMC_REQUIRE(ll && lp && lq && rho_inout_host && n_accept_host, "null pointer");
         ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
         ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
@@ -2601,22 +1684,11 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
     if (!rc) rc = check_mixture(prm->log_q);
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
-    PcnDev pd;
-    memset(&pd, 0, sizeof(pd));
-    pd.bmtab = ctx->d_bmtab;
-    pd.d = prm->d;
-    pd.d_noise = d_noise;
-    pd.beta = prm->beta;
-    pd.mu = prm->mu_dev;
-    pd.L = prm->L_dev;
-    pd.Linv = prm->Linv_dev;
+    PcnDev pd = pcn_dev_from_params(ctx, prm, d_noise);
     pd.ll = to_dev(prm->log_likelihood);
     pd.lp = to_dev(prm->log_prior);
     pd.lq = to_dev(prm->log_q);
-    pd.seed = prm->seed;
-    pd.gid0 = prm->gid0;
     pd.noise = prm->noise;
-    pd.nu = prm->nu;
     pd.mode = PCN_X_STEP;
     ASMC_REQUIRE(pd.noise == ASMC_NOISE_F64 || pd.noise == ASMC_NOISE_F32, "bad noise mode");
     // device step-size cell + history
@@ -2631,7 +1703,7 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
     const double t_b = now();
     ctx->h_pinned[0] = *rho_inout_host;
     ASMC_HIP(hipMemcpyAsync(d_rho, ctx->h_pinned, sizeof(double), hipMemcpyHostToDevice, st));
-    if (asmc_pcn_mm_supported(pd.d, x) && !getenv("ASMC_PCN_GENERIC")) {
+    if (asmc_pcn_mm_supported(pd.d, x) && !pcn_env_generic()) {
         // d = 64 / 128: triangular mat-vecs on the fp64 matrix cores, always on the whitened state
         rc = asmc_pcn_mm_pack(ctx, pd, st);
         if (rc) return rc;
@@ -2667,7 +1739,7 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
     const bool reg_ok = pcn_reg_supported(pd.d, prm->x_dtype == ASMC_F64 ? 8 : 4, x);
     // whitened-state stepping: plain (single-component) targets, enough steps to amortise the two conversions
     const bool single = pd.ll.C == 1 && pd.lp.C == 1 && pd.lq.C == 1;
-    bool y_state = reg_ok && n_steps >= 4 && !getenv("ASMC_PCN_XSTATE");  // several components: only coordinate-major (below)
+    bool y_state = reg_ok && n_steps >= 4 && !pcn_env_xstate();  // several components: only coordinate-major (below)
     // whitened state in a coordinate-major scratch buffer (grown on demand, kept for the life of the ctx)
     const bool soa = y_state && pcn_ensure_ysoa(ctx, n, pd.d, prm->x_dtype, pd, st);
     if (!single && !soa) y_state = false;  // the row-major whitened-state kernel folds single Gaussians only
@@ -2735,7 +1807,7 @@ static int pcn_propose_launch(asmc_ctx* ctx, int64_t n, int d, int x_dtype, cons
     int grid = 0;
     int rc = pcn_prepare_gamma(ctx, n, pd, step, st);
     if (rc) return rc;
-    const bool pad = d > 16 && d < 32 && !getenv("ASMC_PCN_GENERIC");
+    const bool pad = d > 16 && d < 32 && !pcn_env_generic();
     if (pad || (pcn_reg_supported(d, x_dtype == ASMC_F64 ? 8 : 4, x) && ((uintptr_t)x_prop % 16) == 0)) {
         // d in {4, 8, 16, 32}: the register-resident kernel's proposal half (same arithmetic as the fused step);
         // 16 < d < 32: the same kernel compiled for 32 dimensions with identity-padded tables
@@ -2751,7 +1823,7 @@ static int pcn_propose_launch(asmc_ctx* ctx, int64_t n, int d, int x_dtype, cons
         return launch_pcn_step<float, 0>(ctx, n, (float*)const_cast<void*>(x), qf_old, qf_new, nullptr, pd, rho_ptr, step,
                                          nullptr, &grid, nullptr, nullptr, nullptr, st);
     }
-    if (asmc_pcn_mm_supported(d, x) && ((uintptr_t)x_prop % 16) == 0 && ctx->d_mmtab && !getenv("ASMC_PCN_GENERIC")) {
+    if (asmc_pcn_mm_supported(d, x) && ((uintptr_t)x_prop % 16) == 0 && ctx->d_mmtab && !pcn_env_generic()) {
         // d = 64 / 128: both mat-vecs of the proposal on the fp64 matrix cores (the generic LDS kernel took 10 / 76 ms per
         // step at 1M particles - the path every user with Python densities and d > 32 was on)
         pd.noise = ASMC_NOISE_F64;
@@ -2761,53 +1833,23 @@ static int pcn_propose_launch(asmc_ctx* ctx, int64_t n, int d, int x_dtype, cons
                                   pd.nu > 0.0 ? MM_XPROPOSE_T : MM_XPROPOSE, rho_ptr, step, nullptr, &grid, st);
     }
     const int D = pcn_pad_dim(d);
-    if (D != d && D > 0 && D <= ctx->d_max_pad && !(D == 32 && d > 16) && !getenv("ASMC_PCN_GENERIC") && !getenv("ASMC_PCN_NOPAD")) {
+    if (D != d && D > 0 && D <= ctx->d_max_pad && !(D == 32 && d > 16) && !pcn_env_generic() && !pcn_env_nopad()) {
         // any other d <= 128 (17 .. 31 have the in-kernel padding above): zero-padded copies of the rows and of the reference's
         // tables, the D-dimensional proposal kernel with the noise masked beyond d, x' copied back without the padding
-        const size_t es = x_dtype == ASMC_F64 ? 8 : 4;
-        const size_t tab_doubles = (size_t)D + 2 * (size_t)D * D;
-        const size_t tab_bytes = ((tab_doubles * 8 + 255) / 256) * 256;
-        const size_t row_bytes = (((size_t)n * D * es + 255) / 256) * 256;
-        const size_t need = tab_bytes + 2 * row_bytes;
-        if (need > ctx->xpad_bytes) {
-            ASMC_HIP(hipStreamSynchronize(st));
-            if (ctx->d_xpad) (void)hipFree(ctx->d_xpad);
-            ctx->d_xpad = nullptr;
-            ctx->xpad_bytes = 0;
-            if (hipMalloc(&ctx->d_xpad, need) != hipSuccess) {
-                (void)hipGetLastError();
-                asmc_set_error("pcn: no device memory for the zero-padded copies of a proposal (%zu bytes)", need);
-                return ASMC_ERR_NOMEM;
-            }
-            ctx->xpad_bytes = need;
-        }
-        double* tab = reinterpret_cast<double*>(ctx->d_xpad);
-        void* xp = reinterpret_cast<char*>(ctx->d_xpad) + tab_bytes;
-        void* xq = reinterpret_cast<char*>(xp) + row_bytes;
         PcnDev src = pd;
         src.ll.C = src.lp.C = src.lq.C = 0;
-        ASMC_LAUNCH(ctx, st, "k_pad_tables", k_pad_tables, dim3(1), dim3(256), 0, st, d, D, src, tab);
-        ASMC_LAUNCH_CHECK();
-        const int pg = grid_for(n * D, ASMC_BLOCK * 4, ASMC_MAX_BLOCKS * 2);
-        if (es == 8)
-            ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<double>, dim3(pg), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)x, (double*)xp);
-        else
-            ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<float>, dim3(pg), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)x, (float*)xp);
-        ASMC_LAUNCH_CHECK();
+        PcnPadded pad;
+        rc = pcn_pad_problem(ctx, n, d, D, x_dtype, x, src, 0, st, &pad);
+        if (rc) return rc;
         PcnDev p2 = pd;
         p2.d = D;
         p2.d_noise = d;
-        p2.mu = tab;
-        p2.L = tab + D;
-        p2.Linv = p2.L + (size_t)D * D;
-        rc = pcn_propose_launch(ctx, n, D, x_dtype, xp, xq, qf_old, qf_new, p2, rho_ptr, step, st);
+        p2.mu = pad.mu;
+        p2.L = pad.L;
+        p2.Linv = pad.Linv;
+        rc = pcn_propose_launch(ctx, n, D, x_dtype, pad.xp, pad.xq, qf_old, qf_new, p2, rho_ptr, step, st);
         if (rc) return rc;
-        if (es == 8)
-            ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<double>, dim3(pg), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)xq, (double*)x_prop);
-        else
-            ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<float>, dim3(pg), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)xq, (float*)x_prop);
-        ASMC_LAUNCH_CHECK();
-        return ASMC_OK;
+        return launch_unpad_rows(ctx, n, d, D, x_dtype, pad.xq, x_prop, st);
     }
     if (x_dtype == ASMC_F64)
         return launch_pcn_step<double, 1>(ctx, n, (double*)const_cast<void*>(x), nullptr, nullptr, nullptr, pd, rho_ptr,
@@ -2888,16 +1930,7 @@ static int ysplit_pd(asmc_ctx* ctx, int64_t n, const asmc_pcn_params* prm, PcnDe
     ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
     ASMC_REQUIRE(prm->mu_dev && prm->L_dev && prm->Linv_dev, "null reference pointer");
     ASMC_REQUIRE(!(prm->nu > 0.0) || prm->nu >= 1.0, "nu must be >= 1 (or <= 0 for the Gaussian reference)");
-    memset(&pd, 0, sizeof(pd));
-    pd.bmtab = ctx->d_bmtab;
-    pd.d = prm->d;
-    pd.beta = prm->beta;
-    pd.mu = prm->mu_dev;
-    pd.L = prm->L_dev;
-    pd.Linv = prm->Linv_dev;
-    pd.seed = prm->seed;
-    pd.gid0 = prm->gid0;
-    pd.nu = prm->nu;
+    pd = pcn_dev_from_params(ctx, prm, 0);  // (no built-in densities: the caller evaluates its own between propose and accept)
     ASMC_REQUIRE(prm->noise == ASMC_NOISE_F64 || prm->noise == ASMC_NOISE_F32, "bad noise mode");
     pd.noise = prm->noise;  // same in every call of a session: accept regenerates what propose drew
     return ASMC_OK;
@@ -3174,17 +2207,7 @@ static int pcn_mutate_flow_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, d
     double* ll_new = reinterpret_cast<double*>(w + xb + 2 * vb);
     double* lp_new = reinterpret_cast<double*>(w + xb + 3 * vb);
     double* lq_new = reinterpret_cast<double*>(w + xb + 4 * vb);
-    PcnDev pd;
-    memset(&pd, 0, sizeof(pd));
-    pd.bmtab = ctx->d_bmtab;
-    pd.d = d;
-    pd.mu = prm->mu_dev;
-    pd.L = prm->L_dev;
-    pd.Linv = prm->Linv_dev;
-    pd.seed = prm->seed;
-    pd.gid0 = prm->gid0;
-    pd.nu = prm->nu;
-    pd.d_noise = d_noise;
+    PcnDev pd = pcn_dev_from_params(ctx, prm, d_noise);
     double* d_rho = ctx->d_rho;
     double* d_rho_hist = ctx->d_rho + 8;
     long long* d_counts = ctx->d_counts;
@@ -3194,13 +2217,12 @@ static int pcn_mutate_flow_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, d
     // launches - the host enqueues the whole mutation while the reference fit's passes are still running
     // register-resident whitened-state path (d in {4, 8, 16, 32}): x -> y once, then per step
     // propose / flow / accept / adapt, y -> x at the end; four launches per step, no host round trip
-    const bool reg_ok = pcn_reg_supported(d, prm->x_dtype == ASMC_F64 ? 8 : 4, x) && !getenv("ASMC_PCN_XSTATE");
+    const bool reg_ok = pcn_reg_supported(d, prm->x_dtype == ASMC_F64 ? 8 : 4, x) && !pcn_env_xstate();
     if (!reg_ok) {  // (the register path's table pack carries the step size)
         ASMC_LAUNCH(ctx, st, "k_set_scalar", k_set_scalar, dim3(1), dim3(1), 0, st, d_rho, *rho_inout_host);
         ASMC_LAUNCH_CHECK();
     }
     if (reg_ok) {
-        pd.beta = prm->beta;
         pd.ll = to_dev(prm->log_likelihood);
         pd.lp = to_dev(prm->log_prior);
         pd.lq = pd.lp;  // placeholder: the proposal density is the flow
@@ -3360,22 +2382,11 @@ static int pcn_mutate_flow16_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll,
     ASMC_REQUIRE(prm->noise == ASMC_NOISE_F64 || prm->noise == ASMC_NOISE_F32, "bad noise mode");
     ASMC_REQUIRE(ctx->d_mmtab != nullptr && ((uintptr_t)x % 16) == 0, "flow16: ctx was created with d_max <= 32, or a misaligned state");
     hipStream_t st = as_stream(stream);
-    PcnDev pd;
-    memset(&pd, 0, sizeof(pd));
-    pd.bmtab = ctx->d_bmtab;
-    pd.d = prm->d;
-    pd.d_noise = d_noise;
-    pd.beta = prm->beta;
-    pd.mu = prm->mu_dev;
-    pd.L = prm->L_dev;
-    pd.Linv = prm->Linv_dev;
+    PcnDev pd = pcn_dev_from_params(ctx, prm, d_noise);
     pd.ll = to_dev(prm->log_likelihood);
     pd.lp = to_dev(prm->log_prior);
     pd.lq = pd.lp;  // placeholder: the proposal density is the flow
-    pd.seed = prm->seed;
-    pd.gid0 = prm->gid0;
     pd.noise = prm->noise;
-    pd.nu = prm->nu;
     double* d_rho = ctx->d_rho;
     double* d_rho_hist = ctx->d_rho + 8;
     long long* d_counts = ctx->d_counts;
@@ -3418,6 +2429,26 @@ static int pcn_mutate_flow16_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll,
     return mutate_flow_collect(ctx, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st);
 }
 
+// The tail of a flow mutation on a zero-padded copy xp of the state x.  The un-padding copy must sit behind the mutation on the
+// stream AND in front of the read-back's synchronisation: the blocking form returns with x final (it used to synchronise
+// inside the implementation and enqueue the copy after that, so a C caller reading x on another stream saw the padded run's
+// input).  So the implementation always runs deferred here, the copy follows, and the blocking form collects afterwards.
+template <typename Impl>
+static int pcn_flow_padded_tail(asmc_ctx* ctx, int64_t n, int d, int D, int x_dtype, const void* xp, void* x, int n_steps,
+                                double* rho_inout_host, int64_t* n_accept_host, double* rho_hist_host, hipStream_t st, Impl impl) {
+    const int caller_defers = ctx->mutate_defer;
+    ctx->mutate_defer = 1;
+    int rc = impl();
+    ctx->mutate_defer = caller_defers;
+    if (rc) return rc;
+    rc = launch_unpad_rows(ctx, n, d, D, x_dtype, xp, x, st);
+    if (rc) return rc;
+    if (caller_defers) return ASMC_OK;  // asmc_pcn_mutate_flow_result waits for the mutation's event; the copy is stream-ordered behind it
+    ctx->mutate_pending_steps = 0;
+    // (stream synchronisation, not the event recorded in front of the copy: x must be final when this call returns)
+    return mutate_flow_collect(ctx, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st);
+}
+
 extern "C" {
 
 int asmc_pcn_mutate_flow(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, double* lq,
@@ -3436,8 +2467,8 @@ int asmc_pcn_mutate_flow(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* 
     // with a coupling flow (1.2 - 1.8 ms per step at 1M particles) and had no device path for an autoregressive flow there.
     // (... and at d <= 32 when the flow itself lives in that layout: asmc_flow_layout = 1, an autoregressive flow of hidden width 128)
     const bool lay16 = asmc_flow_layout(flow->kind, flow->dims, flow->hidden) == 1;
-    if ((prm->d > 32 || lay16) && prm->d <= 128 && prm->d == flow->dims && ctx->d_mmtab && !getenv("ASMC_PCN_GENERIC") && !getenv("ASMC_PCN_NOPAD") &&
-        !getenv("ASMC_PCN_XSTATE")) {
+    if ((prm->d > 32 || lay16) && prm->d <= 128 && prm->d == flow->dims && ctx->d_mmtab && !pcn_env_generic() && !pcn_env_nopad() &&
+        !pcn_env_xstate()) {
         const int d = prm->d, D = d <= 64 ? 64 : 128;
         asmc_pcn_params p16 = *prm;
         p16.d = D;
@@ -3453,65 +2484,19 @@ int asmc_pcn_mutate_flow(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* 
             if (d == D && ((uintptr_t)x % 16) == 0)
                 return pcn_mutate_flow16_impl(ctx, n, x, ll, lp, lq, prm, flow, n_steps, step0, rho_inout_host, n_accept_host, rho_hist_host,
                                               stream, 0);
-            const size_t es = prm->x_dtype == ASMC_F64 ? 8 : 4;
-            const size_t tab_doubles = (size_t)D + 2 * (size_t)D * D + 3 * 2 * (size_t)ASMC_MAX_COMPONENTS * D;
-            const size_t tab_bytes = ((tab_doubles * 8 + 255) / 256) * 256;
-            const size_t need = tab_bytes + (size_t)n * D * es;
-            if (need > ctx->xpad_bytes) {
-                ASMC_HIP(hipStreamSynchronize(st));
-                if (ctx->d_xpad) (void)hipFree(ctx->d_xpad);
-                ctx->d_xpad = nullptr;
-                ctx->xpad_bytes = 0;
-                if (hipMalloc(&ctx->d_xpad, need) != hipSuccess) {
-                    (void)hipGetLastError();
-                    asmc_set_error("pcn: no device memory for the zero-padded copy of the state (%zu bytes)", need);
-                    return ASMC_ERR_NOMEM;
-                }
-                ctx->xpad_bytes = need;
-            }
-            double* tab = reinterpret_cast<double*>(ctx->d_xpad);
-            void* xp = reinterpret_cast<char*>(ctx->d_xpad) + tab_bytes;
-            PcnDev src;
-            memset(&src, 0, sizeof(src));
-            src.mu = prm->mu_dev, src.L = prm->L_dev, src.Linv = prm->Linv_dev;
-            src.ll = to_dev(prm->log_likelihood), src.lp = to_dev(prm->log_prior);
-            src.lq = src.lp;  // (placeholder: the proposal density is the flow)
-            ASMC_LAUNCH(ctx, st, "k_pad_tables", k_pad_tables, dim3(1), dim3(256), 0, st, d, D, src, tab);
-            ASMC_LAUNCH_CHECK();
-            const int grid = grid_for(n * D, ASMC_BLOCK * 4, ASMC_MAX_BLOCKS * 2);
-            if (es == 8)
-                ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<double>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)x, (double*)xp);
-            else
-                ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<float>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)x, (float*)xp);
-            ASMC_LAUNCH_CHECK();
-            p16.mu_dev = tab;
-            p16.L_dev = tab + D;
-            p16.Linv_dev = p16.L_dev + (size_t)D * D;
-            asmc_mixture* mix[2] = {&p16.log_likelihood, &p16.log_prior};
-            for (int k = 0; k < 2; k++) {
-                mix[k]->mu_dev = p16.Linv_dev + (size_t)D * D + (size_t)k * 2 * ASMC_MAX_COMPONENTS * D;
-                mix[k]->prec_dev = mix[k]->mu_dev + (size_t)ASMC_MAX_COMPONENTS * D;
-            }
-            const int caller_defers = ctx->mutate_defer;  // (the un-padding copy goes in front of the read-back's wait: see below)
-            ctx->mutate_defer = 1;
-            rc = pcn_mutate_flow16_impl(ctx, n, xp, ll, lp, lq, &p16, flow, n_steps, step0, rho_inout_host, n_accept_host, rho_hist_host,
-                                        stream, d);
-            ctx->mutate_defer = caller_defers;
+            void* xp = nullptr;
+            rc = pcn_pad_params(ctx, n, x, prm, D, 2, st, &p16, &xp);
             if (rc) return rc;
-            if (es == 8)
-                ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<double>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)xp, (double*)x);
-            else
-                ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<float>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)xp, (float*)x);
-            ASMC_LAUNCH_CHECK();
-            if (caller_defers) return ASMC_OK;
-            ctx->mutate_pending_steps = 0;
-            return mutate_flow_collect(ctx, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st);
+            return pcn_flow_padded_tail(ctx, n, d, D, prm->x_dtype, xp, x, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st, [&]() {
+                return pcn_mutate_flow16_impl(ctx, n, xp, ll, lp, lq, &p16, flow, n_steps, step0, rho_inout_host, n_accept_host,
+                                              rho_hist_host, stream, d);
+            });
         }
     }
     asmc_pcn_params p2 = *prm;
     p2.d = 32;
-    if (prm->d >= 2 && prm->d < 32 && prm->d == flow->dims && 32 <= ctx->d_max_pad && !getenv("ASMC_PCN_GENERIC") &&
-        !getenv("ASMC_PCN_NOPAD") && asmc_pcn_flow_fused_ok(&p2, flow) && !getenv("ASMC_PCN_AOS") && !getenv("ASMC_PCN_XSTATE")) {
+    if (prm->d >= 2 && prm->d < 32 && prm->d == flow->dims && 32 <= ctx->d_max_pad && !pcn_env_generic() &&
+        !pcn_env_nopad() && asmc_pcn_flow_fused_ok(&p2, flow) && !pcn_env_aos() && !pcn_env_xstate()) {
         ASMC_REQUIRE(ll && lp && lq && rho_inout_host && n_accept_host && work_dev, "null pointer");
         ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
         ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
@@ -3522,71 +2507,22 @@ int asmc_pcn_mutate_flow(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* 
         if (rc) return rc;
         hipStream_t st = as_stream(stream);
         const int d = prm->d, D = 32;
-        const size_t es = prm->x_dtype == ASMC_F64 ? 8 : 4;
-        const size_t tab_doubles = (size_t)D + 2 * (size_t)D * D + 3 * 2 * (size_t)ASMC_MAX_COMPONENTS * D;
-        const size_t tab_bytes = ((tab_doubles * 8 + 255) / 256) * 256;
-        const size_t need = tab_bytes + (size_t)n * D * es;
-        if (need > ctx->xpad_bytes) {
-            ASMC_HIP(hipStreamSynchronize(st));
-            if (ctx->d_xpad) (void)hipFree(ctx->d_xpad);
-            ctx->d_xpad = nullptr;
-            ctx->xpad_bytes = 0;
-            if (hipMalloc(&ctx->d_xpad, need) != hipSuccess) {
-                (void)hipGetLastError();
-                asmc_set_error("pcn: no device memory for the zero-padded copy of the state (%zu bytes)", need);
-                return ASMC_ERR_NOMEM;
-            }
-            ctx->xpad_bytes = need;
-        }
-        double* tab = reinterpret_cast<double*>(ctx->d_xpad);
-        void* xp = reinterpret_cast<char*>(ctx->d_xpad) + tab_bytes;
-        PcnDev src;
-        memset(&src, 0, sizeof(src));
-        src.mu = prm->mu_dev, src.L = prm->L_dev, src.Linv = prm->Linv_dev;
-        src.ll = to_dev(prm->log_likelihood), src.lp = to_dev(prm->log_prior);
-        src.lq = src.lp;  // (placeholder: the proposal density is the flow)
-        ASMC_LAUNCH(ctx, st, "k_pad_tables", k_pad_tables, dim3(1), dim3(256), 0, st, d, D, src, tab);
-        ASMC_LAUNCH_CHECK();
-        const int grid = grid_for(n * D, ASMC_BLOCK * 4, ASMC_MAX_BLOCKS * 2);
-        if (es == 8)
-            ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<double>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)x, (double*)xp);
-        else
-            ASMC_LAUNCH(ctx, st, "k_pad_rows", k_pad_rows<float>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)x, (float*)xp);
-        ASMC_LAUNCH_CHECK();
-        p2.mu_dev = tab;
-        p2.L_dev = tab + D;
-        p2.Linv_dev = p2.L_dev + (size_t)D * D;
-        asmc_mixture* mix[2] = {&p2.log_likelihood, &p2.log_prior};
-        for (int k = 0; k < 2; k++) {
-            mix[k]->mu_dev = p2.Linv_dev + (size_t)D * D + (size_t)k * 2 * ASMC_MAX_COMPONENTS * D;
-            mix[k]->prec_dev = mix[k]->mu_dev + (size_t)ASMC_MAX_COMPONENTS * D;
-        }
-        // The unpadding copy must sit behind the mutation on the stream AND in front of the read-back's synchronisation: the
-        // blocking form returns with x final (it used to synchronise inside the impl and enqueue the copy after
-        // that, so a C caller reading x on another stream saw the padded run's input).  So the impl always runs deferred
-        // here, the copy follows, and the blocking form collects afterwards.
-        const int caller_defers = ctx->mutate_defer;
-        ctx->mutate_defer = 1;
-        rc = pcn_mutate_flow_impl(ctx, n, xp, ll, lp, lq, &p2, flow, work_dev, work_bytes, n_steps, step0, rho_inout_host, n_accept_host,
-                                  rho_hist_host, stream, d);
-        ctx->mutate_defer = caller_defers;
+        void* xp = nullptr;
+        rc = pcn_pad_params(ctx, n, x, prm, D, 2, st, &p2, &xp);
+        if (rc) return rc;
+        rc = pcn_flow_padded_tail(ctx, n, d, D, prm->x_dtype, xp, x, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st, [&]() {
+            return pcn_mutate_flow_impl(ctx, n, xp, ll, lp, lq, &p2, flow, work_dev, work_bytes, n_steps, step0, rho_inout_host,
+                                        n_accept_host, rho_hist_host, stream, d);
+        });
         if (rc == ASMC_ERR_UNSUPPORTED) {
             // the one-kernel step declined after the pre-check (no register path for this pointer, no coordinate-major state): nothing
             // of the caller's has been touched yet (only the padded copy was whitened) - the unpadded path serves the shape, as before
+            // (only the implementation answers this code: the tail's own launches and copies fail with ASMC_ERR_HIP)
             ctx->mutate_pending_steps = 0;
             return pcn_mutate_flow_impl(ctx, n, x, ll, lp, lq, prm, flow, work_dev, work_bytes, n_steps, step0, rho_inout_host,
                                         n_accept_host, rho_hist_host, stream, 0);
         }
-        if (rc) return rc;
-        if (es == 8)
-            ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<double>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const double*)xp, (double*)x);
-        else
-            ASMC_LAUNCH(ctx, st, "k_unpad_rows", k_unpad_rows<float>, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, d, D, (const float*)xp, (float*)x);
-        ASMC_LAUNCH_CHECK();
-        if (caller_defers) return ASMC_OK;  // asmc_pcn_mutate_flow_result waits for the mutation's event; the copy is stream-ordered behind it
-        ctx->mutate_pending_steps = 0;
-        // (stream synchronisation, not the event recorded in front of the copy: x must be final when this call returns)
-        return mutate_flow_collect(ctx, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st);
+        return rc;
     }
     return pcn_mutate_flow_impl(ctx, n, x, ll, lp, lq, prm, flow, work_dev, work_bytes, n_steps, step0, rho_inout_host, n_accept_host,
                                 rho_hist_host, stream, 0);

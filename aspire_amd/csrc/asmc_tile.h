@@ -1,5 +1,5 @@
 // asmc_tile.h — 64-row LDS tiles: coalesced global <-> LDS copies of row-major particle rows and per-lane row access.
-// Shared by the pCN / density kernels (asmc_pcn.hip) and the preconditioning transforms (asmc_transform.hip).
+// Shared by the pCN / density / moment kernels (asmc_pcn.hip, asmc_density.hip, asmc_moments.hip) and the preconditioning transforms (asmc_transform.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,6 +1,6 @@
 """The population moments (asmc_colsum, asmc_centered_gram, asmc_mean_gram*, asmc_colsum_dev, asmc_centered_gram_dev), the device-side
 reference fit (asmc_reference_factor*) and the built-in densities (asmc_mixture_logpdf, asmc_mixture_logpdf_premap,
-asmc_gaussian_draw) of csrc/asmc_pcn.hip and csrc/asmc_pcn_mm.hip on every dispatch path and at the edges, against the long-double
+asmc_gaussian_draw) of csrc/asmc_moments.hip, csrc/asmc_density.hip and csrc/asmc_pcn_mm.hip on every dispatch path and at the edges, against the long-double
 restatement of tests/moments_ref.py.
 
 Shape -> path (s = bytes per element; every case that names an instantiation asserts, from profile_variants, that it ran):
