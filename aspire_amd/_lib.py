@@ -26,11 +26,15 @@ COUNT_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 ASMC_BIS_REC = 40
 ASMC_SELECT_THREADS = 262144
 ASMC_STUDENT_MAX_ROWS = 16384
-ASMC_ABI_VERSION = 26
+ASMC_ABI_VERSION = 27
 ASMC_FLOW_COUPLING, ASMC_FLOW_MAF = 0, 1  # asmc_coupling.kind
 ASMC_MAX_COUNT_CELLS = 64  # asmc_pcn_set_count_cells
 ASMC_CDF_REC = 9
 ASMC_CDF_STATE = 36
+# asmc_nuts_state: slots of its arrays (include/asmc.h)
+ASMC_NUTS_MAX_DOUBLINGS = 10
+ASMC_NUTS_VEC_Z, ASMC_NUTS_VEC_POINT, ASMC_NUTS_VEC_GRAD, ASMC_NUTS_VEC_FIXED = 6, 11, 12, 15
+ASMC_NUTS_SC_DENSITIES, ASMC_NUTS_SC_SLOTS, ASMC_NUTS_INT_SLOTS = 4, 10, 12
 
 
 class AsmcMixture(ctypes.Structure):
@@ -40,6 +44,21 @@ class AsmcMixture(ctypes.Structure):
         ("logw_dev", c_void_p),
         ("mu_dev", c_void_p),
         ("prec_dev", c_void_p),
+    ]
+
+
+class AsmcNutsState(ctypes.Structure):
+    _fields_ = [
+        ("n", c_int64),
+        ("d", c_int32),
+        ("max_doublings", c_int32),
+        ("vec_dev", c_void_p),
+        ("sc_dev", c_void_p),
+        ("ist_dev", c_void_p),
+        ("minv_dev", c_void_p),
+        ("step_size", c_double),
+        ("beta", c_double),
+        ("threshold", c_double),
     ]
 
 
@@ -238,6 +257,18 @@ SIGNATURES = {
         [_vp, _i64, _i, _vp, _vp, _vp, _vp, _d, POINTER(AsmcMixture), POINTER(AsmcMixture), POINTER(AsmcMixture), _vp, _d, _i, _u64,
          _u64, _u32, _i, _i, _vp, _vp],
     ),
+    "asmc_nuts_mix": (
+        _i,
+        [_vp, _i64, _i, _vp, _vp, _vp, _vp, _d, POINTER(AsmcMixture), POINTER(AsmcMixture), POINTER(AsmcMixture), _vp, _d, _i, _d,
+         _u64, _u64, _u32, _i, _i, _i, _vp, _vp],
+    ),
+    "asmc_nuts_stats": (_i, [_vp, _i, _pi64, _vp]),
+    "asmc_nuts_begin": (_i, [_vp, POINTER(AsmcNutsState), _u64, _u64, _u32, _vp]),
+    "asmc_nuts_select": (_i, [_vp, POINTER(AsmcNutsState), _vp]),
+    "asmc_nuts_drift": (_i, [_vp, POINTER(AsmcNutsState), _vp]),
+    "asmc_nuts_leaf": (_i, [_vp, POINTER(AsmcNutsState), _i, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp]),
+    "asmc_nuts_merge": (_i, [_vp, POINTER(AsmcNutsState), _i, _u64, _u64, _u32, _pi64, _vp]),
+    "asmc_nuts_finish": (_i, [_vp, POINTER(AsmcNutsState), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -118,6 +118,9 @@ struct asmc_ctx {
     double* d_rho;                 // [ASMC_MAX_PCN_STEPS + 8] step-size history on device
     unsigned long long* d_stretch; // [ASMC_MAX_PCN_STEPS] accept counts of the steps of a stretch-move mutation (asmc_stretch.hip)
     unsigned long long* d_mh;      // [ASMC_MAX_PCN_STEPS] accept counts of the steps of a random-walk / HMC mutation (asmc_hmc.hip)
+    unsigned long long* d_nuts;    // [4 * ASMC_MAX_PCN_STEPS + 8] statistics of the transitions of a NUTS mutation, 4 per step index; behind them the building-rows cell (asmc_nuts.hip)
+    double* d_nuts_ws;             // U-turn checkpoints of the fused NUTS kernel, one slab per block (grown on demand)
+    size_t nuts_ws_bytes;
     unsigned int* d_tilectr;       // [2 * ASMC_MAX_PCN_STEPS + 2] fused flow-proposal step: tile hand-out counters, blocks-done counters (one each per step), non-finite density count (64-bit)
     unsigned int* d_bar;           // [1024 * 17] arrival counters + the poison cell of the persistent importance-weight kernel's grid barriers (4 KB apart; they only grow)
     unsigned int bar_base[17];     // their values when the next launch starts (top, groups)

@@ -212,6 +212,7 @@ int asmc_ctx_create(asmc_ctx** ctx_out, int device, int64_t n_max, int d_max) {
     dmalloc((void**)&c->d_rho, sizeof(double) * (ASMC_MAX_PCN_STEPS + 8));
     dmalloc((void**)&c->d_stretch, sizeof(unsigned long long) * ASMC_MAX_PCN_STEPS);
     dmalloc((void**)&c->d_mh, sizeof(unsigned long long) * ASMC_MAX_PCN_STEPS);
+    dmalloc((void**)&c->d_nuts, sizeof(unsigned long long) * (4 * ASMC_MAX_PCN_STEPS + 8));
     if (e == hipSuccess) e = hipMemset(c->d_tilectr, 0, ASMC_TILECTR_BYTES);
     dmalloc((void**)&c->d_bar, sizeof(unsigned int) * 1024 * 17);
     if (e == hipSuccess) e = hipMemset(c->d_bar, 0, sizeof(unsigned int) * 1024 * 17);
@@ -258,6 +259,8 @@ int asmc_ctx_destroy(asmc_ctx* c) {
     (void)hipFree(c->d_rho);
     (void)hipFree(c->d_stretch);
     (void)hipFree(c->d_mh);
+    (void)hipFree(c->d_nuts);
+    if (c->d_nuts_ws) (void)hipFree(c->d_nuts_ws);
     (void)hipFree(c->d_tilectr);
     (void)hipFree(c->d_rec);
     (void)hipFree(c->d_bar);

@@ -137,6 +137,22 @@ def pack_maf(lib, dims: int, hidden: int, weights, biases) -> np.ndarray:
     return out
 
 
+
+class NutsState:
+    """Arrays behind an asmc_nuts_state (include/asmc.h): vec [15 + 2 max_doublings, n, d], sc [10, n] fp64, ist [12, n] int32."""
+
+    def __init__(self, engine, n, d, max_doublings, minv, step_size, beta, threshold):
+        dev = engine.device
+        self.vec = torch.zeros((_lib.ASMC_NUTS_VEC_FIXED + 2 * int(max_doublings), n, d), dtype=torch.float64, device=dev)
+        self.sc = torch.zeros((_lib.ASMC_NUTS_SC_SLOTS, n), dtype=torch.float64, device=dev)
+        self.ist = torch.zeros((_lib.ASMC_NUTS_INT_SLOTS, n), dtype=torch.int32, device=dev)
+        self.minv = minv
+        self.z = self.vec[_lib.ASMC_NUTS_VEC_Z]
+        self.key = None
+        self.c = _lib.AsmcNutsState(n, d, int(max_doublings), _dptr(self.vec), _dptr(self.sc), _dptr(self.ist), _dptr(minv), float(step_size),
+                                    float(beta), float(threshold))
+
+
 class HipEngine:
     """One engine per (process, device).  Not thread-safe (the ctx is bound to one host thread)."""
 
@@ -1276,3 +1292,72 @@ class HipEngine:
                                     ctypes.byref(cs[1]), ctypes.byref(cs[2]), _dptr(minv), float(step_size), int(n_leap), int(seed),
                                     int(gid0), int(step0), int(n_steps), int(t0), _dptr(dH), self._stream), "asmc_hmc_mix")
         return dH
+
+    # ---- NUTS of the "blackjax_smc" sampler (include/asmc.h asmc_nuts_*) ----------------------------------------------------------
+    def nuts_mix(self, x, ll, lp, lq, beta: float, t_ll: DeviceMixture, t_lp: DeviceMixture, t_lq: DeviceMixture, minv, step_size: float,
+                 max_doublings: int, threshold: float, seed: int, gid0: int, step0: int, n_steps: int, t0: int = 0,
+                 want_info: bool = False, max_blocks: int = 0):
+        """Transitions step0 .. step0 + n_steps - 1 (at most 256) of NUTS on three built-in mixtures in one launch, in place (fp64
+        rows, d <= 128; statistics of step indices t0 .. t0 + n_steps - 1).  Returns the last transition's (depth, leapfrog steps,
+        flags, position) [n, 4] int32 when asked for.  `max_blocks` caps the grid (0: the default)."""
+        self._chk3(ll, lp, lq)
+        assert x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 2
+        n, d = x.shape
+        info = torch.empty((n, 4), dtype=torch.int32, device=self.device) if want_info else None
+        cs = [m.c_struct() for m in (t_ll, t_lp, t_lq)]
+        check(self.lib.asmc_nuts_mix(self._ctx, n, d, _dptr(x), _dptr(ll), _dptr(lp), _dptr(lq), float(beta), ctypes.byref(cs[0]),
+                                     ctypes.byref(cs[1]), ctypes.byref(cs[2]), _dptr(minv), float(step_size), int(max_doublings),
+                                     float(threshold), int(seed), int(gid0), int(step0), int(n_steps), int(t0), int(max_blocks),
+                                     _dptr(info), self._stream), "asmc_nuts_mix")
+        return info
+
+    def nuts_stats(self, n_steps: int) -> np.ndarray:
+        """[n_steps, 4] (moved rows, leapfrog steps, divergent rows, integer acceptance sum) of step indices 0 .. n_steps - 1 (this
+        rank's particles) - synchronises."""
+        out = np.zeros((n_steps, 4), dtype=np.int64)
+        check(self.lib.asmc_nuts_stats(self._ctx, int(n_steps), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream),
+              "asmc_nuts_stats")
+        return out
+
+    def nuts_state(self, n: int, d: int, max_doublings: int, minv, step_size: float, beta: float, threshold: float):
+        """The device state of a mutation's trees on the split path (asmc_nuts_state), allocated once per mutation.  `.z` is the
+        current point [n, d] the caller takes gradients at."""
+        return NutsState(self, n, d, max_doublings, minv, step_size, beta, threshold)
+
+    def nuts_set_point(self, st, z, g, ll, lp, lq):
+        """The chain's point, its gradient and its three densities, before a mutation's first transition."""
+        st.vec[_lib.ASMC_NUTS_VEC_POINT].copy_(z)
+        st.vec[_lib.ASMC_NUTS_VEC_GRAD].copy_(g)
+        for k, v in enumerate((ll, lp, lq)):
+            st.sc[_lib.ASMC_NUTS_SC_DENSITIES + k].copy_(v)
+
+    def nuts_begin(self, st, seed: int, gid0: int, step: int):
+        st.key = (int(seed), int(gid0), int(step))
+        check(self.lib.asmc_nuts_begin(self._ctx, ctypes.byref(st.c), *st.key, self._stream), "asmc_nuts_begin")
+
+    def nuts_select(self, st):
+        check(self.lib.asmc_nuts_select(self._ctx, ctypes.byref(st.c), self._stream), "asmc_nuts_select")
+
+    def nuts_drift(self, st):
+        check(self.lib.asmc_nuts_drift(self._ctx, ctypes.byref(st.c), self._stream), "asmc_nuts_drift")
+
+    def nuts_leaf(self, st, i: int, g, ll, lp, lq):
+        g = g.to(torch.float64).contiguous()
+        ll, lp, lq = (v.to(torch.float64).contiguous() for v in (ll, lp, lq))
+        check(self.lib.asmc_nuts_leaf(self._ctx, ctypes.byref(st.c), int(i), _dptr(g), _dptr(ll), _dptr(lp), _dptr(lq), *st.key,
+                                      self._stream), "asmc_nuts_leaf")
+
+    def nuts_merge(self, st, j: int) -> int:
+        """Merges the complete sub-trees of doubling `j`; returns the rows still building - synchronises."""
+        out = ctypes.c_int64(0)
+        check(self.lib.asmc_nuts_merge(self._ctx, ctypes.byref(st.c), int(j), *st.key, ctypes.byref(out), self._stream), "asmc_nuts_merge")
+        return int(out.value)
+
+    def nuts_finish(self, st, x, ll, lp, lq, t: int, want_info: bool = False):
+        """Moved rows of x (its dtype) and the carried densities <- the proposal; the statistics of step index `t`."""
+        self._chk3(ll, lp, lq)
+        assert x.is_contiguous() and tuple(x.shape) == (st.c.n, st.c.d)
+        info = torch.empty((st.c.n, 4), dtype=torch.int32, device=self.device) if want_info else None
+        check(self.lib.asmc_nuts_finish(self._ctx, ctypes.byref(st.c), self._xdt(x), _dptr(x), _dptr(ll), _dptr(lp), _dptr(lq), int(t),
+                                        _dptr(info), self._stream), "asmc_nuts_finish")
+        return info

@@ -1,10 +1,10 @@
-"""The `"blackjax_smc"` sampler: the SMC loop of `SMCSampler` with random-walk Metropolis-Hastings or Hamiltonian Monte Carlo as the
-mutation.
+"""The `"blackjax_smc"` sampler: the SMC loop of `SMCSampler` with random-walk Metropolis-Hastings, Hamiltonian Monte Carlo or NUTS as
+the mutation.
 
 `HipBlackJAXSMC` mirrors reference src/aspire/samplers/smc/blackjax.py:13-349.  Every particle is an independent chain on the tempered
-log-target (smc/base.py:507-519); the transitions are this repository's HIP kernels (csrc/asmc_hmc.hip) instead of the third-party
-`blackjax` and `jax` packages, which are absent: parity with their random streams is unpinned.  `"nuts"` is not
-implemented, so the default algorithm here is `"hmc"`.
+log-target (smc/base.py:507-519); the transitions are this repository's HIP kernels (csrc/asmc_hmc.hip, csrc/asmc_nuts.hip) instead of
+the third-party `blackjax` and `jax` packages, which are absent: parity with their random streams is unpinned (DESIGN.md §3.13,
+§3.18).  The default algorithm here is `"hmc"`; the reference's default `"nuts"` runs on request.
 """
 from __future__ import annotations
 
@@ -23,10 +23,12 @@ from .smc import DEFAULT_BETA_TOLERANCE, SMCSampler
 logger = logging.getLogger(__name__)
 
 MAX_CHUNK = 2048  # steps whose accept counts the device holds (ASMC_MAX_PCN_STEPS): one read-back per chunk
+NUTS_MAX_LAUNCH = 256  # transitions of one fused NUTS launch (k_nuts_mix keeps their statistics in LDS)
+NUTS_MAX_DOUBLINGS = 10  # ASMC_NUTS_MAX_DOUBLINGS
 FUSED_MAX_DIMS = 128  # k_hmc_mix keeps a row of up to 128 coordinates in registers
 FUSED_MAX_COMPONENTS = 8  # ASMC_MAX_COMPONENTS
 SAMPLER_KWARGS = ("n_steps", "algorithm", "step_size", "num_integration_steps", "inverse_mass_matrix", "sigma", "n_final_steps",
-                  "flow_sample_on_engine")
+                  "flow_sample_on_engine", "max_num_doublings", "divergence_threshold")
 RW_ALGORITHMS = ("rwmh", "random_walk")
 _default_logged = False
 
@@ -107,6 +109,7 @@ class HipBlackJAXSMC(SMCSampler):
     key = None
     record_dH = False  # diagnostic: keep the energy differences of a mutation's last transition in `last_dH` (a device tensor)
     last_dH = None
+    last_nuts = None  # NUTS, global: leapfrog steps per transition, divergent and moved shares of the last mutation; mean depth of its last transition
 
     @track_calls
     def sample(self, n_samples: int, n_steps: int = None, adaptive: bool = True, target_efficiency: float = 0.5,
@@ -121,9 +124,10 @@ class HipBlackJAXSMC(SMCSampler):
         unknown = sorted(set(self.sampler_kwargs) - set(SAMPLER_KWARGS))
         if unknown:
             raise TypeError(f"sampler_kwargs {unknown} are not supported by the blackjax_smc sampler; supported: "
-                            f"{', '.join(SAMPLER_KWARGS[:6])}")
+                            f"{', '.join(SAMPLER_KWARGS)}")
         if "algorithm" not in self.sampler_kwargs and not _default_logged:
-            logger.info('blackjax_smc: the default algorithm is "hmc" (the reference defaults to "nuts", which is not implemented here)')
+            logger.info('blackjax_smc: the default algorithm is "hmc" (the reference defaults to "nuts", which is available here on '
+                        'request: sampler_kwargs={"algorithm": "nuts"})')
             _default_logged = True
         self.sampler_kwargs.setdefault("n_steps", 5 * self.dims)  # blackjax.py:118
         self.sampler_kwargs.setdefault("algorithm", "hmc")  # (blackjax.py:119: "nuts")
@@ -131,6 +135,8 @@ class HipBlackJAXSMC(SMCSampler):
         self.sampler_kwargs.setdefault("num_integration_steps", 10)  # blackjax.py:284-286
         self.sampler_kwargs.setdefault("inverse_mass_matrix", None)  # blackjax.py:121
         self.sampler_kwargs.setdefault("sigma", 0.1)  # blackjax.py:122
+        self.sampler_kwargs.setdefault("max_num_doublings", 10)  # blackjax.nuts
+        self.sampler_kwargs.setdefault("divergence_threshold", 1000.0)  # blackjax.nuts
         if rng_key is None:
             self.key = 42  # blackjax.py:125-128
         elif isinstance(rng_key, (int, np.integer)) and not isinstance(rng_key, bool):
@@ -161,28 +167,34 @@ class HipBlackJAXSMC(SMCSampler):
     def _check_options(self):
         kw = self.sampler_kwargs
         algorithm = str(kw["algorithm"]).lower()
-        if algorithm == "nuts":
-            raise NotImplementedError('algorithm="nuts" is not implemented by the HIP kernels; use "hmc" or "rwmh"')
+        if algorithm == "nuts" and not hasattr(self.engine, "nuts_mix"):
+            raise NotImplementedError('algorithm="nuts" is not implemented by this engine; use "hmc" or "rwmh"')
         if algorithm in RW_ALGORITHMS:
             self._sigma = proposal_scale(kw["sigma"], self.dims)
             return
-        if algorithm != "hmc":
+        if algorithm not in ("hmc", "nuts"):
             raise ValueError(f"Unsupported algorithm: {algorithm}")  # blackjax.py:321
         self._minv = inverse_mass_diagonal(kw["inverse_mass_matrix"], self.dims)
         if int(kw["num_integration_steps"]) < 1 or not float(kw["step_size"]) > 0.0:
             raise ValueError("num_integration_steps must be >= 1 and step_size positive")
+        if algorithm == "nuts":
+            k = kw["max_num_doublings"]
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= NUTS_MAX_DOUBLINGS:
+                raise ValueError(f"max_num_doublings must be an integer in 1 .. {NUTS_MAX_DOUBLINGS}, got {k!r}")
+            if not float(kw["divergence_threshold"]) > 0.0:  # (a NaN is refused too)
+                raise ValueError(f"divergence_threshold must be positive, got {kw['divergence_threshold']!r}")
         if self._transformed():
-            raise NotImplementedError("algorithm=\"hmc\" needs identity preconditioning: the HIP transform kernels carry no gradient "
-                                      "(use preconditioning=None, or algorithm=\"rwmh\")")
+            raise NotImplementedError(f"algorithm=\"{algorithm}\" needs identity preconditioning: the HIP transform kernels carry no "
+                                      "gradient (use preconditioning=None, or algorithm=\"rwmh\")")
         if self._builtin_densities():
             return
         numpy_callables = [name for name, f in (("log_likelihood", self._log_likelihood), ("log_prior", self._log_prior))
                            if not isinstance(f, DiagGaussianMixture)]
         if numpy_callables and not is_torch_namespace(self.xp):
-            raise TypeError(f"algorithm=\"hmc\" takes gradients by torch.autograd: {' and '.join(numpy_callables)} must be "
+            raise TypeError(f"algorithm=\"{algorithm}\" takes gradients by torch.autograd: {' and '.join(numpy_callables)} must be "
                             "torch-differentiable callables (construct the sampler with xp=torch), or use algorithm=\"rwmh\"")
         if not (isinstance(self.prior_flow, GaussianFlow) or hasattr(self.prior_flow, "_to_latent")):
-            raise TypeError(f"algorithm=\"hmc\" needs a proposal flow with differentiable torch modules, got "
+            raise TypeError(f"algorithm=\"{algorithm}\" needs a proposal flow with differentiable torch modules, got "
                             f"{type(self.prior_flow).__name__}")
 
     # ---- the mutation -------------------------------------------------------------------------------------------------------
@@ -196,15 +208,30 @@ class HipBlackJAXSMC(SMCSampler):
         # one key per mutation: (seed, number of mutations so far); the history travels in checkpoints, so a resumed run goes on
         seed = mutation_seed(self.key if self.key is not None else 42, len(self.history.mcmc_acceptance))
         gid0 = self._gid0(particles)
-        if str(kw["algorithm"]).lower() in RW_ALGORITHMS:
-            x_new, accepted = self._mutate_rw(x, ll, lp, lq, beta, nsteps, seed, gid0)
-        else:
-            self.fit_preconditioning_transform(x)
-            x_new, accepted = self._mutate_hmc(x, ll, lp, lq, beta, nsteps, seed, gid0)
+        algorithm = str(kw["algorithm"]).lower()
         n_global = self._n_global(particles)
-        accepted = self._global_counts([accepted])[0]
-        # blackjax.py:226-227: the mean over particles of the mean over steps = accepts / (particles x steps), over the whole population
-        self.history.mcmc_acceptance.append(float(accepted / (n_global * nsteps)) if nsteps else float("nan"))
+        if algorithm == "nuts":
+            self.fit_preconditioning_transform(x)
+            x_new, stats, depth_sum = self._mutate_nuts(x, ll, lp, lq, beta, nsteps, seed, gid0)
+            moved, steps, divergent, acc, depth_sum = self._global_counts([int(v) for v in stats] + [depth_sum])
+            # NUTSInfo has no is_accepted: the reference records NaN here (blackjax.py:271-277).  Recorded instead: the mean
+            # acceptance statistic of the trees, from integer sums, so equal for every sharding and launch order
+            rows = n_global * nsteps
+            self.history.mcmc_acceptance.append(float(acc / (4294967296.0 * rows)) if nsteps else float("nan"))
+            self.last_nuts = {"mean_depth": float(depth_sum / n_global) if nsteps else float("nan"),  # (of the last transition)
+                              "steps_per_transition": float(steps / rows) if nsteps else float("nan"),
+                              "divergent_share": float(divergent / rows) if nsteps else float("nan"),
+                              "moved_share": float(moved / rows) if nsteps else float("nan")}
+        else:
+            if algorithm in RW_ALGORITHMS:
+                x_new, accepted = self._mutate_rw(x, ll, lp, lq, beta, nsteps, seed, gid0)
+            else:
+                self.fit_preconditioning_transform(x)
+                x_new, accepted = self._mutate_hmc(x, ll, lp, lq, beta, nsteps, seed, gid0)
+            accepted = self._global_counts([accepted])[0]
+            # blackjax.py:226-227: the mean over particles of the mean over steps = accepts / (particles x steps), over the whole
+            # population
+            self.history.mcmc_acceptance.append(float(accepted / (n_global * nsteps)) if nsteps else float("nan"))
         if self._global_counts([e.count_nonfinite(lq)[0]])[0]:
             raise ValueError("Log proposal contains NaN values")  # blackjax.py:346-347
         return self._wrap(x_new, ll, lp, lq, beta, like=particles)
@@ -291,7 +318,56 @@ class HipBlackJAXSMC(SMCSampler):
             accepted += int(e.mh_counts(chunk).sum())
         return x, accepted
 
-    # ---- differentiable densities (split HMC) --------------------------------------------------------------------------------
+    def _mutate_nuts(self, x, ll, lp, lq, beta, nsteps, seed, gid0):
+        """`nsteps` NUTS transitions of every row: (x, the four statistics summed over the transitions, the sum of the last
+        transition's depths), this rank's rows."""
+        e, kw = self.engine, self.sampler_kwargs
+        n, d = x.shape
+        eps, maxd, thr = float(kw["step_size"]), int(kw["max_num_doublings"]), float(kw["divergence_threshold"])
+        minv = None if self._minv is None else e.asarray(self._minv)
+        stats = np.zeros(4, dtype=np.int64)
+        info = None
+        if self._fused_ok(x):
+            # built-in densities: whole transitions in one kernel; one gradient evaluation per launch plus one per leapfrog step
+            self.last_mutation_path = "nuts fused: built-in densities, whole transitions in one kernel (asmc_nuts_mix)"
+            mixes = (self._log_likelihood.device_mixture(e), self._log_prior.device_mixture(e), self.prior_flow.device_mixture(e))
+            for t0 in range(0, nsteps, MAX_CHUNK):
+                chunk = min(MAX_CHUNK, nsteps - t0)
+                for l0 in range(0, chunk, NUTS_MAX_LAUNCH):
+                    k = min(NUTS_MAX_LAUNCH, chunk - l0)
+                    info = e.nuts_mix(x, ll, lp, lq, beta, *mixes, minv, eps, maxd, thr, seed, gid0, t0 + l0, k, t0=l0,
+                                      want_info=t0 + l0 + k == nsteps)
+                    self.n_likelihood_evaluations += n
+                st = e.nuts_stats(chunk).sum(axis=0)
+                self.n_likelihood_evaluations += int(st[1])
+                stats += st
+        else:
+            # everything else: the population in lockstep, gradients by torch.autograd between the launches; one gradient evaluation
+            # per mutation plus one per leaf of the longest tree.  At most max_num_doublings synchronisations per transition
+            self.last_mutation_path = "nuts split: select / drift / leaf / merge launches around torch.autograd gradients (asmc_nuts_*)"
+            if nsteps:
+                z0 = x.to(torch.float64)
+                g0, ll0, lp0, lq0 = self._target_and_grad(z0, beta)
+                st = e.nuts_state(n, d, maxd, minv, eps, beta, thr)
+                e.nuts_set_point(st, z0, g0, ll0, lp0, lq0)
+            for t0 in range(0, nsteps, MAX_CHUNK):
+                chunk = min(MAX_CHUNK, nsteps - t0)
+                for t in range(t0, t0 + chunk):
+                    e.nuts_begin(st, seed, gid0, t)
+                    for j in range(maxd):
+                        e.nuts_select(st)
+                        for i in range(1 << j):
+                            e.nuts_drift(st)
+                            g_new, ll_new, lp_new, lq_new = self._target_and_grad(st.z, beta)
+                            e.nuts_leaf(st, i, g_new, ll_new, lp_new, lq_new)
+                        if e.nuts_merge(st, j) == 0:
+                            break
+                    info = e.nuts_finish(st, x, ll, lp, lq, t - t0, want_info=t == nsteps - 1)
+                stats += e.nuts_stats(chunk).sum(axis=0)
+        depth_sum = int(info[:, 0].sum()) if info is not None else 0
+        return x, stats, depth_sum
+
+    # ---- differentiable densities (split HMC, split NUTS) --------------------------------------------------------------------------------
     def _flow_log_prob_torch(self, x: torch.Tensor) -> torch.Tensor:
         """log q(x) through the flow's differentiable torch modules (the path training uses), fp64 outside the flow's layers."""
         f = self.prior_flow

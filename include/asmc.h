@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 26
+#define ASMC_ABI_VERSION 27
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -860,6 +860,78 @@ int asmc_hmc_mix(asmc_ctx* ctx, int64_t n, int d, void* x_dev, double* ll_dev, d
                  const asmc_mixture* log_likelihood, const asmc_mixture* log_prior, const asmc_mixture* log_q,
                  const double* minv_dev, double step_size, int n_leap, uint64_t seed, uint64_t gid0, uint32_t step0, int n_steps,
                  int t0, double* dH_out_dev, asmc_stream stream);
+
+/* ---- NUTS mutation of the "blackjax_smc" sampler (ABI 27) --------------------------------------------------------------------
+ * Replace blackjax.nuts inside BlackJAXSMC.mutate (reference src/aspire/samplers/smc/blackjax.py:119, 229-277: the reference's
+ * default algorithm): one independent chain per particle on the tempered log-target of smc/base.py:507-519.  blackjax and jax are
+ * absent: no parity with their random streams; the transition below is this repository's reading.
+ * Energy E(z, p) = 1/2 p^T M^-1 p - L(z), L the guarded tempered target of asmc_mh_accept, M^-1 = diag(minv_dev) or the identity.
+ * Streams of particle gid = gid0 + i at transition `step` under the mutation's key `seed`: the momenta p0 are asmc_hmc_momentum's;
+ *   the tree's blocks have the counter {gid lo, gid hi, step, 0x60000000 | k}, uniforms U(w[0], w[1]):
+ *     k = 0: bit j of word 0 set: doubling j goes forward (v = +1), clear: backward;  k = 1 + j: u_tree[j];
+ *     k = 16 + m: u_leaf[m], m the leapfrog steps of this transition taken before the leaf (0 .. 1022).
+ * Transition: a start whose L is not finite leaves the row, takes no step, counts as not moved.  Otherwise both edges and the
+ *   proposal are the start (position 0), tree_lw = 0, psum = p0.  Doubling j, while depth < max_doublings: from the edge on side v,
+ *   2^j velocity-Verlet steps of size v step_size.  Leaf i: delta = E_i - E0; !(delta <= threshold): DIVERGENT, the transition ends
+ *   and the sub-tree is dropped; else lw = -delta joins the acceptance sum as min(1, exp(lw)), new = logaddexp(sub_lw, lw), the leaf
+ *   becomes the sub-tree's proposal if i == 0 or u_leaf[m] < exp(lw - new), sub_lw = new, sub_psum += p_i.  Sub-tree U-turn tests by
+ *   checkpoints: top = popcount(i >> 1); even i stores (p_i, sub_psum) in checkpoint top; odd i with r trailing one bits tests
+ *   turning(ckpt_p[k], p_i, sub_psum - ckpt_psum[k] + ckpt_p[k]) for k = top .. top - r + 1; a hit ends the transition as TURNING.
+ *   turning(a, b, s) = a^T M^-1 s <= 0 or b^T M^-1 s <= 0.  A complete sub-tree replaces the edge on side v; the tree's proposal
+ *   becomes the sub-tree's if u_tree[j] < exp(min(0, sub_lw - tree_lw)); tree_lw = logaddexp(tree_lw, sub_lw), psum += sub_psum,
+ *   depth += 1; TURNING if turning(p_left, p_right, psum).  The row becomes the proposal (point, three densities, gradient): no
+ *   Metropolis step.  Per row: depth, leapfrog steps, flags (1 divergent, 2 turning), the proposal's signed position along the
+ *   trajectory (moved: position != 0).
+ * Statistics: transition index t (0 <= t < 2048, its place in the current chunk) owns four device counters: moved rows, leapfrog
+ *   steps, divergent rows, and the integer sum over rows of round(2^32 acceptance_sum / leaves) (0 without leaves; order-independent,
+ *   at most 2^52 at 2^20 rows).  asmc_nuts_mix zeroes counters t0 .. t0 + n_steps - 1, asmc_nuts_finish those of t;
+ *   asmc_nuts_stats reads [n_steps][4] back (synchronises).
+ * asmc_nuts_mix: transitions step0 .. step0 + n_steps - 1 (n_steps <= 256 per launch) in ONE launch for three diagonal Gaussian
+ *   mixtures, fp64 state, d <= 128; rows and carried densities read / written once per launch, the start's densities recomputed at x
+ *   (asmc_hmc_mix's rule).  max_blocks > 0 caps the grid (0: one block per compute unit); the checkpoints live in a workspace of the
+ *   context indexed by block.  info_out_dev [n, 4] (optional): depth, steps, flags, position of the last transition.
+ * Split path (any differentiable target; the population in lockstep).  asmc_nuts_state: vec_dev [ASMC_NUTS_VEC_FIXED +
+ *   2 max_doublings][n][d], sc_dev [ASMC_NUTS_SC_SLOTS][n] (fp64), ist_dev [ASMC_NUTS_INT_SLOTS][n] (int32), allocated by the caller
+ *   once per mutation.  The caller writes the chain's point into vec slot ASMC_NUTS_VEC_POINT, its gradient into ASMC_NUTS_VEC_GRAD
+ *   and (ll, lp, lq) into sc slots ASMC_NUTS_SC_DENSITIES .. + 2 before the first transition; every transition leaves its proposal
+ *   there.  Per transition: asmc_nuts_begin; per doubling j: asmc_nuts_select (the building rows' edge -> the current point, slot
+ *   ASMC_NUTS_VEC_Z; empty sub-tree), per leaf i: asmc_nuts_drift (half kick and drift of the rows whose sub-tree is alive), the
+ *   caller's gradient and densities at slot ASMC_NUTS_VEC_Z (all rows; ended rows hold their proposal there), asmc_nuts_leaf (second
+ *   half kick, divergence test, leaf sampling, checkpoint store or U-turn tests); asmc_nuts_merge (*building_host <- rows still
+ *   building; synchronises: once per doubling).  asmc_nuts_finish: moved rows of x_dev (x_dtype, rounded) and ll / lp / lq <- the
+ *   proposal; the statistics of step index t; info_out_dev as above. */
+#define ASMC_NUTS_MAX_DOUBLINGS 10
+#define ASMC_NUTS_VEC_Z 6
+#define ASMC_NUTS_VEC_POINT 11
+#define ASMC_NUTS_VEC_GRAD 12
+#define ASMC_NUTS_VEC_FIXED 15
+#define ASMC_NUTS_SC_DENSITIES 4
+#define ASMC_NUTS_SC_SLOTS 10
+#define ASMC_NUTS_INT_SLOTS 12
+typedef struct asmc_nuts_state {
+    int64_t n;
+    int d, max_doublings;
+    double* vec_dev;
+    double* sc_dev;
+    int* ist_dev;
+    const double* minv_dev; /* [d] diagonal of M^-1 or NULL */
+    double step_size, beta, threshold;
+} asmc_nuts_state;
+int asmc_nuts_mix(asmc_ctx* ctx, int64_t n, int d, void* x_dev, double* ll_dev, double* lp_dev, double* lq_dev, double beta,
+                  const asmc_mixture* log_likelihood, const asmc_mixture* log_prior, const asmc_mixture* log_q,
+                  const double* minv_dev, double step_size, int max_doublings, double threshold, uint64_t seed, uint64_t gid0,
+                  uint32_t step0, int n_steps, int t0, int max_blocks, int* info_out_dev, asmc_stream stream);
+int asmc_nuts_stats(asmc_ctx* ctx, int n_steps, int64_t* stats_host, asmc_stream stream);
+int asmc_nuts_begin(asmc_ctx* ctx, const asmc_nuts_state* state, uint64_t seed, uint64_t gid0, uint32_t step, asmc_stream stream);
+int asmc_nuts_select(asmc_ctx* ctx, const asmc_nuts_state* state, asmc_stream stream);
+int asmc_nuts_drift(asmc_ctx* ctx, const asmc_nuts_state* state, asmc_stream stream);
+int asmc_nuts_leaf(asmc_ctx* ctx, const asmc_nuts_state* state, int leaf, const double* g_new_dev, const double* ll_new_dev,
+                   const double* lp_new_dev, const double* lq_new_dev, uint64_t seed, uint64_t gid0, uint32_t step,
+                   asmc_stream stream);
+int asmc_nuts_merge(asmc_ctx* ctx, const asmc_nuts_state* state, int doubling, uint64_t seed, uint64_t gid0, uint32_t step,
+                    int64_t* building_host, asmc_stream stream);
+int asmc_nuts_finish(asmc_ctx* ctx, const asmc_nuts_state* state, int x_dtype, void* x_dev, double* ll_dev, double* lp_dev,
+                     double* lq_dev, int t, int* info_out_dev, asmc_stream stream);
 
 #ifdef __cplusplus
 }
