@@ -74,9 +74,13 @@ __global__ __launch_bounds__(ASMC_BLOCK) void k_pcn_step(
             // y' = a y + rho sqrt(s) xi (s = 1 for the Gaussian reference), q1 = |y'|^2
             double q1 = 0.0;
             const double rs = tpcn_scale(rho, p.nu, q0, p.gam, i);
+            const bool fast_noise = p.noise == ASMC_NOISE_F32;  // wave-uniform: the same stream as the register-resident kernels
             for (int qd = 0; 4 * qd < d; qd++) {
                 double z[4];
-                normal_quad(p.seed, gid, step, (uint32_t)qd, bmt, z[0], z[1], z[2], z[3]);
+                if (fast_noise)
+                    normal_quad_f32(p.seed, gid, step, (uint32_t)qd, z[0], z[1], z[2], z[3]);
+                else
+                    normal_quad(p.seed, gid, step, (uint32_t)qd, bmt, z[0], z[1], z[2], z[3]);
                 for (int e = 0; e < 4 && 4 * qd + e < d; e++) {
                     const double ye = fma(rs, z[e], a * v[(4 * qd + e) * 64]);
                     v[(4 * qd + e) * 64] = ye;
@@ -1300,6 +1304,19 @@ static int dispatch_pcn_reg_flow(asmc_ctx* ctx, int64_t n, T* y, T* x_prop, doub
     return ASMC_ERR_UNSUPPORTED;
 }
 
+// LDS of one wave of the generic kernel: its 64-row tile and the 64 x d work vectors.  Widths that have no other kernel
+// (d > 128) are checked against the budget by the entry points, before anything is launched.
+static size_t pcn_generic_wave_bytes(int d, size_t elem) { return (size_t)64 * lds_row_stride(d * (int)elem) + (size_t)64 * 8 * d; }
+static bool pcn_generic_fits(int d, size_t elem) { return pcn_generic_wave_bytes(d, elem) <= 160 * 1024 - 1024 - BM_TAB_N * 16; }
+static int pcn_generic_check(int d, int x_dtype) {
+    const size_t elem = x_dtype == ASMC_F64 ? 8 : 4;
+    if (d > 128 && !pcn_generic_fits(d, elem)) {
+        asmc_set_error("pcn: d=%d needs %zu B of LDS per wave (unsupported)", d, pcn_generic_wave_bytes(d, elem));
+        return ASMC_ERR_UNSUPPORTED;
+    }
+    return ASMC_OK;
+}
+
 template <typename T, int PHASE>
 static int launch_pcn_step(asmc_ctx* ctx, int64_t n, T* x, double* ll, double* lp, double* lq, const PcnDev& pd,
                            const double* rho_ptr, uint32_t step, long long* block_counts, int* grid_out,
@@ -1356,10 +1373,10 @@ static int launch_pcn_step(asmc_ctx* ctx, int64_t n, T* x, double* ll, double* l
         asmc_set_error("pcn: no kernel for mode %d at d=%d, noise=%d", pd.mode, pd.d, pd.noise);
         return ASMC_ERR_UNSUPPORTED;
     }
-    const size_t per_wave = (size_t)64 * lds_row_stride(rowbytes) + (size_t)64 * 8 * pd.d;
+    const size_t per_wave = pcn_generic_wave_bytes(pd.d, sizeof(T));
     size_t lds_bytes = 0;
     const int wpb = waves_for_lds(per_wave, &lds_bytes);
-    if (per_wave > 160 * 1024 - 1024 - BM_TAB_N * 16) {
+    if (!pcn_generic_fits(pd.d, sizeof(T))) {
         asmc_set_error("pcn: d=%d needs %zu B of LDS per wave (unsupported)", pd.d, per_wave);
         return ASMC_ERR_UNSUPPORTED;
     }
@@ -1682,6 +1699,7 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
     int rc = check_mixture(prm->log_likelihood);
     if (!rc) rc = check_mixture(prm->log_prior);
     if (!rc) rc = check_mixture(prm->log_q);
+    if (!rc) rc = pcn_generic_check(prm->d, prm->x_dtype);  // (before the Gamma draw of a tpCN step)
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
     PcnDev pd = pcn_dev_from_params(ctx, prm, d_noise);
@@ -1866,6 +1884,8 @@ int asmc_pcn_propose(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x
     ASMC_REQUIRE(n > 0 && n <= ctx->n_max && d > 0 && d <= ASMC_MAX_DIMS, "bad sizes");
     ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
     ASMC_REQUIRE(rho >= 0.0 && rho <= 1.0, "rho must be in (0, 1], or 0 for the device-resident step size");
+    const int fits = pcn_generic_check(d, x_dtype);
+    if (fits) return fits;
     hipStream_t st = as_stream(stream);
     PcnDev pd;
     memset(&pd, 0, sizeof(pd));

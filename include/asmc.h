@@ -94,7 +94,13 @@ typedef struct {
                                  updates applied in blocks of k steps (see asmc_pcn_set_count_cells) */
     int32_t noise;            /* ASMC_NOISE_F64: fp64 Box-Muller, 2 normals / Philox block (1e-15 parity with
                                  the oracle); ASMC_NOISE_F32: fp32 hardware Box-Muller, 4 normals / block
-                                 (fast; honoured by the register-resident kernels, d in {4,8,16,32}) */
+                                 (fast).  asmc_pcn_mutate honours the mode on every path - register-resident,
+                                 matrix-core and the generic LDS kernel (unaligned x, d > 128, ASMC_PCN_GENERIC /
+                                 ASMC_PCN_NOPAD) draw the same stream, normals and Gamma variates alike: where a
+                                 buffer lies never changes what is sampled.  asmc_pcn_propose takes no mode and
+                                 always draws ASMC_NOISE_F64.  The generic kernel holds a 64-row tile and 64 work
+                                 vectors per wave in LDS: fp64 d > 152 and fp32 d > 202 return
+                                 ASMC_ERR_UNSUPPORTED before anything is launched */
     double nu;                /* > 0 (>= 1): t-preconditioned Crank-Nicolson, the reference's default step_fn="tpcn"
                                  (smc/minipcn.py:46-49): the reference distribution is Student-t(mu, L L^T, nu); the
                                  proposal noise is scaled by sqrt(s), s ~ InvGamma((d + nu)/2, (nu + |y|^2)/2), and the
