@@ -26,7 +26,7 @@ COUNT_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 ASMC_BIS_REC = 40
 ASMC_SELECT_THREADS = 262144
 ASMC_STUDENT_MAX_ROWS = 16384
-ASMC_ABI_VERSION = 27
+ASMC_ABI_VERSION = 28
 ASMC_FLOW_COUPLING, ASMC_FLOW_MAF = 0, 1  # asmc_coupling.kind
 ASMC_MAX_COUNT_CELLS = 64  # asmc_pcn_set_count_cells
 ASMC_CDF_REC = 9
@@ -35,6 +35,7 @@ ASMC_CDF_STATE = 36
 ASMC_NUTS_MAX_DOUBLINGS = 10
 ASMC_NUTS_VEC_Z, ASMC_NUTS_VEC_POINT, ASMC_NUTS_VEC_GRAD, ASMC_NUTS_VEC_FIXED = 6, 11, 12, 15
 ASMC_NUTS_SC_DENSITIES, ASMC_NUTS_SC_SLOTS, ASMC_NUTS_INT_SLOTS = 4, 10, 12
+ASMC_CHAIN_ROWS, ASMC_CHAIN_YS = 0, 1  # asmc_chain_record: source
 
 
 class AsmcMixture(ctypes.Structure):
@@ -79,6 +80,22 @@ class AsmcPcnParams(ctypes.Structure):
         ("adapt", c_int32),
         ("noise", c_int32),
         ("nu", c_double),
+    ]
+
+
+class AsmcChainTarget(ctypes.Structure):
+    _fields_ = [
+        ("x_dev", c_void_p),
+        ("ll_dev", c_void_p),
+        ("lp_dev", c_void_p),
+        ("n_slots", c_int64),
+        ("n", c_int64),
+        ("pitch", c_int64),
+        ("slot0", c_int64),
+        ("d", c_int32),
+        ("x_dtype", c_int32),
+        ("stride", c_int32),
+        ("reserved", c_int32),
     ]
 
 
@@ -269,6 +286,10 @@ SIGNATURES = {
     "asmc_nuts_leaf": (_i, [_vp, POINTER(AsmcNutsState), _i, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp]),
     "asmc_nuts_merge": (_i, [_vp, POINTER(AsmcNutsState), _i, _u64, _u64, _u32, _pi64, _vp]),
     "asmc_nuts_finish": (_i, [_vp, POINTER(AsmcNutsState), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "asmc_chain_record": (_i, [_vp, POINTER(AsmcChainTarget), _i64, _i, _vp, _vp, _vp, POINTER(AsmcPcnParams), POINTER(AsmcTransform),
+                               _vp]),
+    "asmc_chain_set": (_i, [_vp, POINTER(AsmcChainTarget)]),
+    "asmc_chain_clear": (_i, [_vp]),
 }
 
 _lib = None

@@ -171,7 +171,24 @@ struct asmc_ctx {
     double* h_gram;    // [128 + 128 * 128] doubles: asmc_mean_gram's results (sum | Gram) until asmc_mean_gram_fetch
     double* d_ref;     // the same on the device (d_small / d_partials are every other call's scratch): asmc_reference_factor
     int gram_pending_d;  // d of an enqueued, not yet fetched asmc_mean_gram (0: none)
+    // chain recorder (asmc_chain.hip): the target asmc_pcn_mutate's step loop honours (asmc_chain_set), and its scratch
+    int chain_on;
+    asmc_chain_target chain;
+    double* d_chain_lq;            // [chain_lq_n] where a recording un-whitening launch leaves the log q it re-evaluates
+    int64_t chain_lq_n;
+    void* d_chain_rows;            // [chain_rows_bytes] n rows of the padded width: where a zero-padded call un-whitens for the recorder
+    size_t chain_rows_bytes;
 };
+
+// asmc_chain.hip: rows [n, d] of src (row-major, x_dtype) and their carried densities -> slot `slot` of the chain
+int asmc_chain_rows_launch(asmc_ctx* ctx, const asmc_chain_target* c, int64_t slot, const void* src, const double* ll,
+                           const double* lp, hipStream_t st);
+// ... the carried densities alone (the rows come from another launch)
+int asmc_chain_scalars_launch(asmc_ctx* ctx, const asmc_chain_target* c, int64_t slot, const double* ll, const double* lp,
+                              hipStream_t st);
+// asmc_pcn.hip: the un-whitening launch of asmc_pcn_ysplit_end with its output pointed at x_out [n, d]; `repack`: pack the
+// parameter tables first, as asmc_pcn_ysplit_end does (the recorder packs them only when someone else has since)
+int asmc_pcn_ysplit_unwhiten(asmc_ctx* ctx, int64_t n, void* x_out, const asmc_pcn_params* prm, bool repack, hipStream_t st);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: the "already raised" guards of the launchers
 // are kept per device (a process with contexts on two devices must raise it on both)

@@ -255,6 +255,8 @@ int asmc_ctx_destroy(asmc_ctx* c) {
     if (c->h_student) (void)hipHostFree(c->h_student);
     if (c->d_ysoa) (void)hipFree(c->d_ysoa);
     if (c->d_xpad) (void)hipFree(c->d_xpad);
+    if (c->d_chain_lq) (void)hipFree(c->d_chain_lq);
+    if (c->d_chain_rows) (void)hipFree(c->d_chain_rows);
     (void)hipFree(c->d_counts);
     (void)hipFree(c->d_rho);
     (void)hipFree(c->d_stretch);

@@ -1701,6 +1701,14 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
     if (!rc) rc = check_mixture(prm->log_q);
     if (!rc) rc = pcn_generic_check(prm->d, prm->x_dtype);  // (before the Gamma draw of a tpCN step)
     if (rc) return rc;
+    const asmc_chain_target& ch = ctx->chain;
+    const bool padded = d_noise != 0;  // (then prm->d is the padded width and x the padded copy)
+    const size_t row_bytes = (size_t)prm->d * (prm->x_dtype == ASMC_F64 ? 8 : 4);
+    if (ctx->chain_on) {  // asmc_chain_set: every recorded slot of this call inside the chain
+        ASMC_REQUIRE(ch.n == n && ch.d == (padded ? d_noise : prm->d) && ch.x_dtype == prm->x_dtype, "chain target: n, d or dtype differ from the call's");
+        ASMC_REQUIRE(ch.slot0 >= 0 && ch.slot0 + n_steps / ch.stride <= ch.n_slots, "chain target: the call's steps do not fit the chain");
+        ASMC_REQUIRE(!padded || ctx->chain_rows_bytes >= (size_t)n * row_bytes, "chain target: no scratch for the padded rows");
+    }
     hipStream_t st = as_stream(stream);
     PcnDev pd = pcn_dev_from_params(ctx, prm, d_noise);
     pd.ll = to_dev(prm->log_likelihood);
@@ -1721,6 +1729,26 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
     const double t_b = now();
     ctx->h_pinned[0] = *rho_inout_host;
     ASMC_HIP(hipMemcpyAsync(d_rho, ctx->h_pinned, sizeof(double), hipMemcpyHostToDevice, st));
+    // Slot of step t of this call (asmc_chain_set).  Not whitened: the rows are x itself (un-padded on their way when the call
+    // runs on a zero-padded copy).  Whitened: the call's own un-whitening launch `unwhiten(rec)` with the slot's rows (the padded
+    // scratch, un-padded behind it) and density rows as its outputs rec[0 .. 3]; a launch that un-whitens x where it lies
+    // (`in_place`: the matrix-core and the row-major register kernels) gets a copy of the state there first.  The state itself is
+    // only read.  These are the launches that end a call of t + 1 steps: the same bits.
+    auto record_state = [&](int t, bool whitened, bool in_place, auto&& unwhiten) -> int {
+        const int64_t slot = ch.slot0 + t / ch.stride;
+        char* slot_x = static_cast<char*>(ch.x_dev) + (size_t)slot * (size_t)n * (size_t)ch.pitch * (row_bytes / prm->d);
+        if (!whitened) {
+            if (!padded) return asmc_chain_rows_launch(ctx, &ch, slot, x, ll, lp, st);
+            const int r = launch_unpad_rows(ctx, n, d_noise, prm->d, prm->x_dtype, x, slot_x, st);
+            return r ? r : asmc_chain_scalars_launch(ctx, &ch, slot, ll, lp, st);
+        }
+        void* dst = padded ? ctx->d_chain_rows : slot_x;
+        if (in_place) ASMC_HIP(hipMemcpyAsync(dst, x, (size_t)n * row_bytes, hipMemcpyDeviceToDevice, st));
+        void* rec[4] = {dst, ch.ll_dev + (size_t)slot * (size_t)n, ch.lp_dev + (size_t)slot * (size_t)n, ctx->d_chain_lq};
+        const int r = unwhiten(rec);
+        if (r || !padded) return r;
+        return launch_unpad_rows(ctx, n, d_noise, prm->d, prm->x_dtype, dst, slot_x, st);
+    };
     if (asmc_pcn_mm_supported(pd.d, x) && !pcn_env_generic()) {
         // d = 64 / 128: triangular mat-vecs on the fp64 matrix cores, always on the whitened state
         rc = asmc_pcn_mm_pack(ctx, pd, st);
@@ -1736,6 +1764,14 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
             if (rc) return rc;
             rc = pcn_close_step(ctx, st, grid, d_block, n, t, d_counts, d_rho, d_rho_hist, prm->target_accept, prm->adapt, t == n_steps - 1);
             if (rc) return rc;
+            if (ctx->chain_on && t % ch.stride == ch.stride - 1) {
+                rc = record_state(t, true, true, [&](void* const* rec) -> int {
+                    int g2 = 0;
+                    return asmc_pcn_mm_launch(ctx, n, prm->x_dtype, rec[0], (double*)rec[1], (double*)rec[2], (double*)rec[3], pd, MM_UNWHITEN,
+                                              d_rho, 0, d_block, &g2, st);
+                });
+                if (rc) return rc;
+            }
         }
         rc = asmc_pcn_mm_launch(ctx, n, prm->x_dtype, x, ll, lp, lq, pd, MM_UNWHITEN, d_rho, 0, d_block, &grid, st);
         if (rc) return rc;
@@ -1761,7 +1797,9 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
     // whitened state in a coordinate-major scratch buffer (grown on demand, kept for the life of the ctx)
     const bool soa = y_state && pcn_ensure_ysoa(ctx, n, pd.d, prm->x_dtype, pd, st);
     if (!single && !soa) y_state = false;  // the row-major whitened-state kernel folds single Gaussians only
-    auto launch_mode = [&](int mode, uint32_t stp, int* grid) -> int {
+    // `rec`: the launch works on rec[0] (rows) and rec[1 .. 3] (ll, lp, lq) instead of the population's arrays - the chain
+    // recorder's use of the un-whitening epilogue (record_state)
+    auto launch_mode = [&](int mode, uint32_t stp, int* grid, void* const* rec = nullptr) -> int {
         if (soa) mode = mode == PCN_WHITEN ? PCN_WHITEN_S : mode == PCN_UNWHITEN ? PCN_UNWHITEN_S
                         : mode == PCN_Y_STEP ? (single ? PCN_Y_STEP_S : PCN_Y_STEP_SG)
                         : mode == PCN_Y_STEP_T ? (single ? PCN_Y_STEP_TS : PCN_Y_STEP_TSG) : mode;
@@ -1769,11 +1807,15 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
         const int nz = pd.noise;
         if (mode == PCN_WHITEN || mode == PCN_UNWHITEN || mode == PCN_UNWHITEN_X || mode == PCN_WHITEN_S || mode == PCN_UNWHITEN_S)
             pd.noise = ASMC_NOISE_F64;
+        void* xo = rec ? rec[0] : x;
+        double* llo = rec ? (double*)rec[1] : ll;
+        double* lpo = rec ? (double*)rec[2] : lp;
+        double* lqo = rec ? (double*)rec[3] : lq;
         int r;
         if (prm->x_dtype == ASMC_F64)
-            r = launch_pcn_step<double, 0>(ctx, n, (double*)x, ll, lp, lq, pd, d_rho, stp, d_block, grid, nullptr, nullptr, nullptr, st);
+            r = launch_pcn_step<double, 0>(ctx, n, (double*)xo, llo, lpo, lqo, pd, d_rho, stp, d_block, grid, nullptr, nullptr, nullptr, st);
         else
-            r = launch_pcn_step<float, 0>(ctx, n, (float*)x, ll, lp, lq, pd, d_rho, stp, d_block, grid, nullptr, nullptr, nullptr, st);
+            r = launch_pcn_step<float, 0>(ctx, n, (float*)xo, llo, lpo, lqo, pd, d_rho, stp, d_block, grid, nullptr, nullptr, nullptr, st);
         pd.noise = nz;
         return r;
     };
@@ -1794,6 +1836,13 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
         if (rc) return rc;
         rc = pcn_close_step(ctx, st, grid, d_block, n, t, d_counts, d_rho, d_rho_hist, prm->target_accept, prm->adapt, t == n_steps - 1);
         if (rc) return rc;
+        if (ctx->chain_on && t % ch.stride == ch.stride - 1) {
+            rc = record_state(t, y_state, y_state && !soa, [&](void* const* rec) -> int {
+                int g2 = 0;
+                return launch_mode(PCN_UNWHITEN, 0, &g2, rec);
+            });
+            if (rc) return rc;
+        }
     }
     if (y_state) {
         rc = launch_mode(PCN_UNWHITEN, 0, &grid);
@@ -2120,18 +2169,24 @@ int asmc_pcn_ysplit_accept(asmc_ctx* ctx, int64_t n, const asmc_pcn_params* prm,
                           prm->adapt);
 }
 
-int asmc_pcn_ysplit_end(asmc_ctx* ctx, int64_t n, void* x, const asmc_pcn_params* prm, asmc_stream stream) {
+}  // extern "C"
+
+// y -> x_out [n, d] of the open session (the state is only read): asmc_pcn_ysplit_end's launch, and the chain recorder's
+int asmc_pcn_ysplit_unwhiten(asmc_ctx* ctx, int64_t n, void* x, const asmc_pcn_params* prm, bool repack, hipStream_t st) {
     PcnDev pd;
     int rc = ysplit_pd(ctx, n, prm, pd);
     if (rc) return rc;
     ASMC_REQUIRE(x != nullptr && ctx->d_ysoa != nullptr, "null pointer / no session");
-    hipStream_t st = as_stream(stream);
+    ASMC_REQUIRE(repack || pcn_reg_supported(pd.d, prm->x_dtype == ASMC_F64 ? 8 : 4, x), "x_out: a 16-byte aligned buffer of a session's d");
     pd.ys = ctx->d_ysoa;
     pd.n_pad = ((n + 63) / 64) * 64;
     pd.mode = PCN_UNWHITEN_XS;
     pd.noise = ASMC_NOISE_F64;
-    rc = pack_pcn_tables(ctx, pd, st);
-    if (rc) return rc;
+    if (repack || ctx->ptab_tag == 0 || ctx->ptab_tag != ctx->ysplit_seq) {
+        rc = pack_pcn_tables(ctx, pd, st);
+        if (rc) return rc;
+        if (!repack) ctx->ptab_tag = ctx->ysplit_seq;  // (as asmc_pcn_ysplit_propose: the session's tables are back)
+    }
     int grid = 0;
     long long* d_block = ctx->d_counts + ASMC_MAX_PCN_STEPS;
     if (prm->x_dtype == ASMC_F64)
@@ -2139,6 +2194,12 @@ int asmc_pcn_ysplit_end(asmc_ctx* ctx, int64_t n, void* x, const asmc_pcn_params
                                           nullptr, nullptr, st);
     return launch_pcn_step<float, 0>(ctx, n, (float*)x, nullptr, nullptr, nullptr, pd, ctx->d_rho, 0, d_block, &grid, nullptr, nullptr,
                                      nullptr, st);
+}
+
+extern "C" {
+
+int asmc_pcn_ysplit_end(asmc_ctx* ctx, int64_t n, void* x, const asmc_pcn_params* prm, asmc_stream stream) {
+    return asmc_pcn_ysplit_unwhiten(ctx, n, x, prm, true, as_stream(stream));
 }
 
 int asmc_pcn_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x, const void* x_prop, double* ll, double* lp,
@@ -2476,6 +2537,10 @@ int asmc_pcn_mutate_flow(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* 
                          int n_steps, uint32_t step0, double* rho_inout_host, int64_t* n_accept_host,
                          double* rho_hist_host, asmc_stream stream) {
     ASMC_REQUIRE(ctx && x && prm && flow, "null pointer");
+    if (ctx->chain_on) {  // (an MCMC target has no proposal-density term: nothing to record from the flow-proposal step)
+        asmc_set_error("asmc_pcn_mutate_flow: the chain recorder is honoured by asmc_pcn_mutate only (asmc_chain_clear first)");
+        return ASMC_ERR_UNSUPPORTED;
+    }
     ASMC_REQUIRE(flow->affine == ASMC_AFFINE_TANH || (flow->affine == ASMC_AFFINE_SOFTCLIP && flow->kind == ASMC_FLOW_MAF),
                  "bad affine form (the soft-clipped form is for autoregressive flows)");
     // Fewer than 32 dimensions: the one-kernel step on a zero-padded copy (pcn_mutate_padded's scheme: padded rows and tables,

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (ASMC_CDF_EXACT, ASMC_CDF_FAST, ASMC_F32, ASMC_F64, AsmcCoupling, AsmcMixture, AsmcPcnParams,
+from ._lib import (ASMC_CDF_EXACT, ASMC_CDF_FAST, ASMC_F32, ASMC_F64, AsmcChainTarget, AsmcCoupling, AsmcMixture, AsmcPcnParams,
                    AsmcTransform, check)
 
 CDF_MODES = {"exact": ASMC_CDF_EXACT, "fast": ASMC_CDF_FAST}
@@ -93,6 +93,32 @@ class DeviceTransform:
         return AsmcTransform(self.d, self.hints, self.kind.data_ptr(), self.periodic.data_ptr(), self.lower.data_ptr(),
                              self.upper.data_ptr(), None if self.mean is None else self.mean.data_ptr(),
                              None if self.std is None else self.std.data_ptr(), self.eps, self.unit_logj, self.affine_logj)
+
+
+@dataclass
+class DeviceChain:
+    """A device chain of the MCMC samplers (include/asmc.h asmc_chain_target): rows x [n_slots, n, pitch >= d] of which the first
+    `d` elements are the walker's coordinates (a view with a longer row stride is a pitched chain), ll / lp [n_slots, n] fp64."""
+
+    x: torch.Tensor
+    ll: torch.Tensor | None
+    lp: torch.Tensor | None
+
+    def __post_init__(self):
+        x = self.x
+        assert x.dim() == 3 and x.stride(2) == 1 and x.stride(0) == x.shape[1] * x.stride(1) and x.stride(1) >= x.shape[2]
+        for v in (self.ll, self.lp):
+            assert v is None or (v.dtype == torch.float64 and v.is_contiguous() and tuple(v.shape) == tuple(x.shape[:2]))
+
+    @property
+    def d(self) -> int:
+        return int(self.x.shape[2])
+
+    def c_struct(self, slot0: int = 0, stride: int = 1) -> AsmcChainTarget:
+        x = self.x
+        return AsmcChainTarget(x.data_ptr(), None if self.ll is None else self.ll.data_ptr(),
+                               None if self.lp is None else self.lp.data_ptr(), int(x.shape[0]), int(x.shape[1]), int(x.stride(1)),
+                               int(slot0), self.d, ASMC_F64 if x.dtype == torch.float64 else ASMC_F32, int(stride), 0)
 
 
 def pack_coupling(lib, dims: int, hidden: int, weights, biases) -> np.ndarray:
@@ -1211,6 +1237,41 @@ class HipEngine:
         check(self.lib.asmc_stretch_counts(self._ctx, int(n_steps), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream),
               "asmc_stretch_counts")
         return out
+
+    # ---- chain recorder of the "minipcn" / "emcee" samplers (include/asmc.h asmc_chain_*) -----------------------------------------
+    def free_memory(self) -> int:
+        """Bytes of device memory that an allocation can still get."""
+        return int(torch.cuda.mem_get_info(self.device)[0])
+
+    def chain_alloc(self, n_slots: int, n: int, d: int, dtype=torch.float64) -> DeviceChain:
+        return DeviceChain(torch.empty((n_slots, n, d), dtype=dtype, device=self.device), self.empty((n_slots, n)),
+                           self.empty((n_slots, n)))
+
+    def chain_record(self, chain: DeviceChain, slot: int, x=None, ll=None, lp=None, sess=None, transform: DeviceTransform | None = None):
+        """Slot `slot` <- the walkers' state: row-major `x` [n, d] (rows of z = T(x) with `transform`), or the whitened state of
+        the open `pcn_ysplit_*` session `sess`; `ll` / `lp`: the carried densities."""
+        n, d = chain.x.shape[1], chain.d
+        for v in (ll, lp):
+            assert v is None or (v.dtype == torch.float64 and v.is_contiguous() and v.numel() == n)
+        ts = transform.c_struct() if transform is not None else None
+        c = chain.c_struct()
+        if sess is None:
+            assert x.dtype == chain.x.dtype and x.is_contiguous() and tuple(x.shape) == (n, d)
+            rc = self.lib.asmc_chain_record(self._ctx, ctypes.byref(c), int(slot), _lib.ASMC_CHAIN_ROWS, _dptr(x), _dptr(ll), _dptr(lp),
+                                            None, ctypes.byref(ts) if ts is not None else None, self._stream)
+        else:
+            assert tuple(sess["x"].shape) == (n, d) and sess["x"].dtype == chain.x.dtype
+            rc = self.lib.asmc_chain_record(self._ctx, ctypes.byref(c), int(slot), _lib.ASMC_CHAIN_YS, None, _dptr(ll), _dptr(lp),
+                                            ctypes.byref(sess["prm"]), None, self._stream)
+        check(rc, "asmc_chain_record")
+
+    def chain_set(self, chain: DeviceChain, slot0: int, stride: int = 1):
+        """From now on `pcn_mutate` records step t of a call (t % stride == stride - 1) into slot slot0 + t // stride."""
+        c = chain.c_struct(slot0=slot0, stride=stride)
+        check(self.lib.asmc_chain_set(self._ctx, ctypes.byref(c)), "asmc_chain_set")
+
+    def chain_clear(self):
+        check(self.lib.asmc_chain_clear(self._ctx), "asmc_chain_clear")
 
     # ---- random-walk MH and HMC of the "blackjax_smc" sampler (include/asmc.h asmc_rw_* / asmc_mh_* / asmc_hmc_*) ---------------
     def rw_propose(self, x, sigma, seed: int, gid0: int, step: int, t: int):

@@ -336,3 +336,63 @@ class MCMCSampler(Sampler):
         # set after construction (as the reference does, mcmc.py:82-87) so no IS weights are formed
         out.log_likelihood, out.log_prior, out.log_q = llv, lpv, lqv
         return out
+
+    chain_checkpoint_path = "checkpoint"  # mcmc.py:17-23: where a chain checkpoint lies in its file
+    chain_dataset_name = "mcmc_chain"
+
+    def log_prob(self, z):
+        """samplers/mcmc.py:112-126: the target of a chain in the preconditioned space, log L + log pi at x = T^-1(z) plus
+        log|det dT^-1/dz|; NaN and +inf count as -inf, as in every accept kernel of this package."""
+        e = self.engine
+        x, logj = self.preconditioning_transform.inverse(z)
+        x = e.asarray(x, dtype=self.x_torch_dtype)
+        lp, ll = self._eval_prior_likelihood(x)
+        r = ll + lp if logj is None else ll + lp + e.asarray(logj)
+        r = torch.where(r < np.inf, r, torch.full_like(r, -np.inf)).reshape(-1)
+        return r if is_torch_namespace(self.xp) else to_numpy(r)
+
+    def default_mcmc_chain_file_checkpoint_callback(self, file_path):
+        """samplers/mcmc.py:128-167: the chain as a native samples group `checkpoint/mcmc_chain` of an HDF5 file (replaced on
+        every call), with `chain_shape`, `iteration`, `stage` and `sampler` as the group's attributes.  A `.pkl` path has no groups:
+        the pickled state (samples included, `chain_shape` with them) is the file, as for every other sampler here."""
+        if file_path is None:
+            return self.default_checkpoint_callback
+        plain = self.default_file_checkpoint_callback(file_path)  # (checks the extension first)
+        path = self._rank_path(file_path)
+        if not path.name.lower().endswith((".h5", ".hdf5")):
+            return plain
+
+        def _callback(state: dict) -> None:
+            from ..io import open_h5
+
+            samples = state.get("samples")
+            if samples is None:
+                raise ValueError("Checkpoint missing samples.")
+            chain_path = f"{self.chain_checkpoint_path}/{self.chain_dataset_name}"
+            with open_h5(path, "a") as h5_file:
+                if chain_path in h5_file:
+                    del h5_file[chain_path]
+                samples.save(h5_file, path=chain_path, flat=False)
+                attrs = h5_file[chain_path].attrs
+                if getattr(samples, "chain_shape", None) is not None:
+                    attrs["chain_shape"] = np.asarray(samples.chain_shape, dtype=int)
+                if state.get("iteration") is not None:
+                    attrs["iteration"] = int(state["iteration"])
+                if state.get("meta", {}).get("stage") is not None:
+                    attrs["stage"] = str(state["meta"]["stage"])
+                if state.get("sampler") is not None:
+                    attrs["sampler"] = str(state["sampler"])
+            self.default_checkpoint_callback(state)
+
+        return _callback
+
+    def checkpoint_mcmc_chain(self, samples, iteration: int | None = None, checkpoint_callback=None,
+                              checkpoint_every: int | None = None, checkpoint_file_path: str | None = None) -> None:
+        """samplers/mcmc.py:169-191."""
+        if checkpoint_every is not None and checkpoint_every <= 0:
+            return
+        if checkpoint_callback is None and checkpoint_file_path is not None:
+            checkpoint_callback = self.default_mcmc_chain_file_checkpoint_callback(checkpoint_file_path)
+        if checkpoint_callback is None:
+            return
+        checkpoint_callback(self.build_checkpoint_state(samples=samples, iteration=iteration, meta={"stage": "mcmc_chain"}))

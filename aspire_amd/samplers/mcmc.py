@@ -1,0 +1,276 @@
+"""The `"minipcn"` and `"emcee"` samplers: plain MCMC from the proposal flow's draws, every step of every walker kept on the device.
+
+`HipMiniPCN` and `HipEmcee` mirror reference src/aspire/samplers/mcmc.py:203-348 (`Emcee`, `MiniPCN`).  The transitions are this
+repository's pCN / tpCN step kernels and stretch-move kernels (csrc/asmc_pcn*.hip, csrc/asmc_stretch.hip) at beta = 1 with a zero
+log q array - the target of an MCMC run has no proposal-density term, so the flow's density is never evaluated after the initial
+draw - and the chain is written by the recorder of csrc/asmc_chain.hip.  Neither `minipcn` nor `emcee` is installed: the chains
+are this repository's specification, parity with the packages' random streams is unpinned.
+"""
+from __future__ import annotations
+
+import logging
+import math
+
+import numpy as np
+import torch
+
+from .._xp import is_torch_namespace
+from ..history import SMCHistory
+from ..samples import MCMCSamples, Samples
+from ..targets import DiagGaussianMixture
+from .base import IdentityTransform, MCMCSampler, track_calls
+from .emcee_smc import MAX_CHUNK, RED_BLUE_MESSAGE, stretch_move_settings
+from .smc import HipSMC
+
+logger = logging.getLogger(__name__)
+
+class ChainSampler(MCMCSampler):
+    """What the two samplers share: one rank only, the memory guard, the preconditioned start, the containers."""
+
+    last_mutation_path = None
+
+    def _single_rank(self):
+        if self.comm.sharded:
+            raise NotImplementedError(f"the {type(self).__name__} sampler runs on one rank: a sharded chain recorder is not "
+                                      "implemented (the SMC samplers shard)")
+
+    def _check_chain_memory(self, n_slots: int, n_walkers: int):
+        """Before anything is allocated: the chain's rows and its two density arrays against the device's free memory."""
+        elem = 4 if self.x_torch_dtype == torch.float32 else 8
+        need = int(n_slots) * int(n_walkers) * (self.dims * elem + 16)
+        free = int(self.engine.free_memory())
+        if need > free:
+            raise ValueError(f"the chain of {n_slots} steps x {n_walkers} walkers x {self.dims} dimensions needs {need} bytes of "
+                             f"device memory and {free} bytes are free; use last_step_only=True (where the sampler has it), "
+                             "fewer steps or fewer walkers")
+
+    def _start(self, n_walkers: int):
+        """Initial walkers from the flow (mcmc.py:49-110) and their image in the preconditioned space: (x, z, logj, ll, lp, T or
+        None).  z is x itself, and logj None, when the transform is the identity."""
+        e, T = self.engine, self.preconditioning_transform
+        init = self.draw_initial_samples(n_walkers)
+        x = init.x if init.x.is_contiguous() else init.x.contiguous()
+        ll, lp = e.asarray(init.log_likelihood).clone(), e.asarray(init.log_prior).clone()
+        if isinstance(T, IdentityTransform) or getattr(T, "is_identity", False):
+            self.fit_preconditioning_transform(x)
+            return x, x.clone(), None, ll, lp, None
+        if getattr(T, "engine", None) is None and hasattr(T, "engine"):
+            T.engine = e
+        z = e.asarray(T.fit(x), dtype=x.dtype)
+        return x, z, e.asarray(T.inverse(z)[1]), ll, lp, T
+
+    def _record(self, chain, slot, z, ll, lp, T):
+        """Slot <- the row-major state: a copy, or T^-1 of it by the transform's own kernels where T has device tables."""
+        e = self.engine
+        if T is None:
+            e.chain_record(chain, slot, x=z, ll=ll, lp=lp)
+        elif hasattr(T, "_tables"):
+            e.chain_record(chain, slot, x=z, ll=ll, lp=lp, transform=T._tables()[1])
+        else:
+            e.chain_record(chain, slot, x=e.asarray(T.inverse(z)[0], dtype=z.dtype), ll=ll, lp=lp)
+
+    def _densities(self, z_prop, T, zeros):
+        """(ll', lp', lq' = 0, log|J|' or None) at the proposals; the flow is not asked."""
+        e = self.engine
+        if T is None:
+            x_prop, logj_new = z_prop, None
+        else:
+            x_prop, logj_new = T.inverse(z_prop)
+            x_prop, logj_new = e.asarray(x_prop, dtype=z_prop.dtype), e.asarray(logj_new)
+        lp_new, ll_new = self._eval_prior_likelihood(x_prop)
+        return ll_new, lp_new, zeros[:z_prop.shape[0]], logj_new
+
+    def _out(self, samples):
+        return samples if is_torch_namespace(self.xp) else samples.to_numpy()
+
+
+class HipMiniPCN(ChainSampler):
+    """The `"minipcn"` sampler (mcmc.py:267-348) on the pCN / tpCN step kernels.
+
+    Specification: the reference distribution of the proposal - Gaussian for `pcn`, Student-t by the EM of
+    student_t.py for `tpcn` - is fitted once, to the initial walkers in z = T(x); the step size starts at min(2.38 / sqrt(d), 0.99)
+    and adapts after every step by `pcn_adapt`; noise and accept streams are the pCN streams of walker i at step t, keyed by one
+    seed drawn from `rng`; chain[t] is the state after transition t + 1."""
+
+    _fit_reference = HipSMC._fit_reference
+    _fit_reference_gaussian = HipSMC._fit_reference_gaussian
+    _upload_reference = HipSMC._upload_reference
+    _check_reference_fit = HipSMC._check_reference_fit
+
+    @track_calls
+    def sample(self, n_samples: int | None = None, n_walkers: int | None = None, rng=None, target_acceptance_rate=0.234,
+               n_steps=100, thin=1, burnin=0, last_step_only=False, step_fn="tpcn", checkpoint_callback=None,
+               checkpoint_every: int | None = None, checkpoint_file_path: str | None = None):
+        self._single_rank()
+        if step_fn not in ("pcn", "tpcn"):
+            raise NotImplementedError(f"step_fn={step_fn!r} is not implemented by the HIP step kernels; use step_fn='tpcn' or 'pcn'")
+        e = self.engine
+        rng = rng or self.rng or np.random.default_rng()
+        if not (n_walkers or n_samples):
+            raise ValueError("give n_walkers or n_samples: the number of walkers defaults to n_samples")
+        n_walkers, n_steps = int(n_walkers or n_samples), int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1")
+        if not last_step_only:
+            self._check_chain_memory(n_steps, n_walkers)
+        self.history = SMCHistory()
+        self.sampler_kwargs = {"step_fn": step_fn}
+        self._pcn_state = {"rho": min(2.38 / math.sqrt(self.dims), 0.99), "step": 0, "nu": None}
+        _, z, logj, ll, lp, T = self._start(n_walkers)
+        mu, L, Linv, nu = self._fit_reference(z, n_walkers, step_fn)
+        seed = int(rng.integers(0, 2**63 - 1, dtype=np.int64))
+        chain = None if last_step_only else e.chain_alloc(n_steps, n_walkers, self.dims, z.dtype)
+        lq, zeros = e.full(n_walkers, 0.0), e.full(n_walkers, 0.0)
+        run = (z, logj, ll, lp, lq, zeros, T, mu, L, Linv, nu, seed, n_steps, float(target_acceptance_rate), chain)
+        builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
+        if T is None and builtin:  # (as HipSMC: the fused kernel at every d; also when nothing is recorded)
+            acc = self._steps_fused(run)
+        elif T is None:
+            acc = self._steps_ysplit(run)  # (the session declines other widths than 4, 8, 16, 32: the row-major path then)
+        else:
+            acc = self._steps_generic(run)
+        self._check_reference_fit()
+        self.history.mcmc_acceptance.append(float(np.mean(acc)) / n_walkers)
+        self.history.mcmc_step_size.append(float(self._pcn_state["rho"]))
+        if last_step_only:
+            x = z if T is None else e.asarray(T.inverse(z)[0], dtype=z.dtype)
+            out = Samples(x=x, xp=torch, parameters=self.parameters)
+            out.log_likelihood, out.log_prior = ll, lp  # (set afterwards: no importance weights)
+            return self._out(out)
+        full = self._out(MCMCSamples.from_chain(chain=chain.x, log_likelihood=chain.ll, log_prior=chain.lp, parameters=self.parameters,
+                                                xp=torch, dtype=self.dtype, thin=1, burn_in=0))
+        self.checkpoint_mcmc_chain(samples=full, iteration=n_steps, checkpoint_callback=checkpoint_callback,
+                                   checkpoint_every=checkpoint_every, checkpoint_file_path=checkpoint_file_path)
+        out = full.post_process(burn_in=burnin, thin=thin)
+        if n_samples is not None:
+            logger.info(f"Subsampling MCMC samples to {n_samples} samples after burn-in and thinning.")
+            out = out[:n_samples]
+        return out
+
+    def _steps_fused(self, run):
+        """Built-in mixture densities, any d: the whole step loop inside asmc_pcn_mutate, which records into the chain target
+        set on the context.  The kernel wants a log q mixture; at beta = 1 its value has no weight (the likelihood's
+        stands in)."""
+        e = self.engine
+        z, logj, ll, lp, lq, zeros, T, mu, L, Linv, nu, seed, n_steps, target, chain = run
+        self.last_mutation_path = "built-in densities: device-side step loop (asmc_pcn_mutate), recorded by its chain target"
+        t_ll, t_lp = self._log_likelihood.device_mixture(e), self._log_prior.device_mixture(e)
+        st, acc, done = self._pcn_state, [], 0
+        try:
+            while done < n_steps:
+                chunk = min(n_steps - done, MAX_CHUNK)
+                if chain is not None:
+                    e.chain_set(chain, done, 1)
+                n_acc, _, st["rho"] = e.pcn_mutate(z, ll, lp, lq, 1.0, mu, L, Linv, t_ll, t_lp, t_ll, seed, 0, st["rho"], chunk, done,
+                                                   target, 1, "f64", nu)
+                acc.extend(n_acc.tolist())
+                done += chunk
+        finally:
+            if chain is not None:
+                e.chain_clear()
+        self.n_likelihood_evaluations += n_steps * z.shape[0]
+        return acc
+
+    def _steps_ysplit(self, run):
+        """Callables, d in {4, 8, 16, 32}: the whitened-state session; the recorder reads the session's state."""
+        e = self.engine
+        z, logj, ll, lp, lq, zeros, T, mu, L, Linv, nu, seed, n_steps, target, chain = run
+        st, acc, done, n = self._pcn_state, [], 0, z.shape[0]
+        while done < n_steps:
+            chunk = min(n_steps - done, MAX_CHUNK)
+            sess = e.pcn_ysplit_begin(z, 1.0, mu, L, Linv, seed, 0, st["rho"], target, True, nu, "f64")
+            if sess is None:
+                return acc + self._steps_generic(run, done)
+            self.last_mutation_path = "callables: whitened-state session (asmc_pcn_ysplit_*), recorded from the session's state"
+            for t in range(done, done + chunk):
+                x_prop = e.pcn_ysplit_propose(sess, t)
+                ll_new, lp_new, lq_new, _ = self._densities(x_prop, None, zeros)
+                e.pcn_ysplit_accept(sess, t, ll, lp, lq, ll_new, lp_new, lq_new, n, t - done)
+                if chain is not None:
+                    e.chain_record(chain, t, sess=sess, ll=ll, lp=lp)
+            n_acc, _, st["rho"] = e.pcn_ysplit_end(sess, chunk)
+            acc.extend(n_acc.tolist())
+            done += chunk
+        return acc
+
+    def _steps_generic(self, run, done: int = 0):
+        """Every other case, and every chain in a preconditioned space: propose / densities / accept on the row-major state."""
+        e = self.engine
+        z, logj, ll, lp, lq, zeros, T, mu, L, Linv, nu, seed, n_steps, target, chain = run
+        builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
+        self.last_mutation_path = ("preconditioned chain (z = T(x)): " if T is not None else "") + \
+            ("built-in densities by their own kernel: " if builtin else "callables: ") + \
+            "split propose / accept with the step closed on the stream (asmc_pcn_split_*), recorded from the rows"
+        st, acc, n = self._pcn_state, [], z.shape[0]
+        while done < n_steps:
+            chunk = min(n_steps - done, MAX_CHUNK)
+            e.pcn_split_begin(st["rho"])
+            for t in range(done, done + chunk):
+                z_prop, q0, q1 = e.pcn_propose(z, mu, L, Linv, 0.0, seed, 0, t, nu=nu)
+                ll_new, lp_new, lq_new, logj_new = self._densities(z_prop, T, zeros)
+                e.pcn_accept(z, z_prop, ll, lp, lq, ll_new, lp_new, lq_new, q0, q1, 1.0, seed, 0, t, logj_old=logj, logj_new=logj_new,
+                             want_count=False)
+                e.pcn_split_adapt(n, target, t - done, True)
+                if chain is not None:
+                    self._record(chain, t, z, ll, lp, T)
+            n_acc, _, st["rho"] = e.pcn_split_end(chunk)
+            acc.extend(n_acc.tolist())
+            done += chunk
+        return acc
+
+
+EMCEE_KWARGS = ("progress", "moves", "live_dangerously")
+
+
+class HipEmcee(ChainSampler):
+    """The `"emcee"` sampler (mcmc.py:203-264): emcee's default move, StretchMove(a) on RedBlueMove(nsplits=2,
+    randomize_split=True), by the stretch kernels on log_prob of the preconditioned space.  One step is two
+    half-sweeps; the recorder runs after the second.  `moves` / `live_dangerously`: the rules of `HipEmceeSMC`."""
+
+    @track_calls
+    def sample(self, n_samples: int | None = None, nwalkers: int | None = None, nsteps: int = 500, rng=None, discard=0,
+               checkpoint_callback=None, checkpoint_every: int | None = None, checkpoint_file_path: str | None = None, **kwargs):
+        self._single_rank()
+        unknown = sorted(set(kwargs) - set(EMCEE_KWARGS))
+        if unknown:
+            raise TypeError(f"keyword arguments {unknown} are not supported by the emcee sampler; supported: {', '.join(EMCEE_KWARGS)}")
+        a, move_live = stretch_move_settings(kwargs.get("moves"))
+        e = self.engine
+        rng = rng or self.rng or np.random.default_rng()
+        if not (nwalkers or n_samples):
+            raise ValueError("give nwalkers or n_samples: the number of walkers defaults to n_samples")
+        nwalkers, nsteps, discard = int(nwalkers or n_samples), int(nsteps), int(discard)
+        if not 0 <= discard < nsteps:
+            raise ValueError(f"discard must be in 0 .. nsteps - 1, got {discard} of {nsteps} steps")
+        if nwalkers < 2 * self.dims and not (kwargs.get("live_dangerously", False) or move_live):
+            raise RuntimeError(RED_BLUE_MESSAGE)
+        if nwalkers < 2:
+            raise ValueError(f"the stretch move needs at least two walkers, got {nwalkers}")
+        self._check_chain_memory(nsteps - discard, nwalkers)
+        self.history = SMCHistory()
+        _, z, logj, ll, lp, T = self._start(nwalkers)
+        seed = int(rng.integers(0, 2**63 - 1, dtype=np.int64))
+        chain = e.chain_alloc(nsteps - discard, nwalkers, self.dims, z.dtype)  # get_chain(discard): those steps are not kept
+        lq, zeros = e.full(nwalkers, 0.0), e.full(nwalkers, 0.0)
+        self.last_mutation_path = "stretch move: propose / densities / accept per half-sweep (asmc_stretch_*), recorded from the rows"
+        accepted = 0
+        for t0 in range(0, nsteps, MAX_CHUNK):
+            chunk = min(MAX_CHUNK, nsteps - t0)
+            for t in range(t0, t0 + chunk):
+                for half in (0, 1):
+                    y, logf = e.stretch_propose(z, half, a, seed, 0, t, t - t0)
+                    ll_new, lp_new, lq_new, logj_new = self._densities(y, T, zeros)
+                    e.stretch_accept(z, half, y, logf, 1.0, ll, lp, lq, ll_new, lp_new, lq_new, seed, 0, t, t - t0, logj=logj,
+                                     logj_new=logj_new)
+                if t >= discard:
+                    self._record(chain, t - discard, z, ll, lp, T)
+            accepted += int(e.stretch_counts(chunk).sum())
+        self.history.mcmc_acceptance.append(float(accepted / (nwalkers * nsteps)))
+        out = self._out(MCMCSamples.from_chain(chain=chain.x, log_likelihood=chain.ll, log_prior=chain.lp, parameters=self.parameters,
+                                               xp=torch, dtype=self.dtype, burn_in=discard))
+        self.checkpoint_mcmc_chain(samples=out, iteration=nsteps, checkpoint_callback=checkpoint_callback,
+                                   checkpoint_every=checkpoint_every, checkpoint_file_path=checkpoint_file_path)
+        if n_samples is not None:
+            logger.info(f"Subsampling MCMC samples to {n_samples} samples after burn-in.")
+            out = out[:n_samples]
+        return out

@@ -361,6 +361,102 @@ class Samples(BaseSamples):
 
 
 @dataclass
+class MCMCSamples(BaseSamples):
+    """samples.py:599-806 - the container of the "minipcn" / "emcee" samplers.  The rows of a chain [..., d] lie flattened in `x`
+    (first axis slowest); `chain_shape` is the chain's shape without the parameter axis, so `chain` is a view of `x`."""
+
+    chain_shape: tuple | None = None
+    thin: int | None = None
+    burn_in: int | None = None
+    autocorrelation_time: Any | None = None
+
+    def __post_init__(self):
+        super().__post_init__()
+        if self.chain_shape is None:
+            self.chain_shape = (len(self.x),)
+        else:
+            self.chain_shape = tuple(int(v) for v in np.asarray(self.chain_shape).reshape(-1))  # (an HDF5 file returns an array)
+            if math.prod(self.chain_shape) != len(self.x):
+                raise ValueError("chain_shape does not match the number of samples")
+
+    @classmethod
+    def from_chain(cls, chain, log_likelihood=None, log_prior=None, log_q=None, parameters=None, xp=None, dtype=None, device=None,
+                   thin: int | None = None, burn_in: int | None = None, autocorrelation_time=None, **extra):
+        """A chain [..., d] ([n_steps, d], or [n_steps, n_walkers, d] for an ensemble) and, optionally, per-row values shaped
+        like the chain without its last axis."""
+        if xp is None:
+            xp = namespace_of(chain)
+        chain = asarray(chain, xp, device=device if is_torch_namespace(xp) else None)
+        if chain.ndim < 2:
+            raise ValueError("chain must have at least 2 dimensions")
+        flat = lambda v: None if v is None else asarray(v, xp, device=device if is_torch_namespace(xp) else None).reshape(-1)  # noqa: E731
+        return cls(x=chain.reshape(-1, chain.shape[-1]), log_likelihood=flat(log_likelihood), log_prior=flat(log_prior),
+                   log_q=flat(log_q), parameters=parameters, xp=xp, device=device, dtype=dtype,
+                   chain_shape=tuple(chain.shape[:-1]), thin=thin, burn_in=burn_in, autocorrelation_time=autocorrelation_time,
+                   **extra)
+
+    @property
+    def chain(self):
+        return self.x.reshape(*self.chain_shape, self.dims)
+
+    @property
+    def n_steps(self) -> int:
+        return self.chain_shape[0]
+
+    @property
+    def n_chains(self) -> int:
+        return self.chain_shape[1] if len(self.chain_shape) > 1 else 1
+
+    def _meta(self) -> dict:
+        return dict(thin=self.thin, burn_in=self.burn_in, autocorrelation_time=self.autocorrelation_time)
+
+    def post_process(self, burn_in: int = 0, thin: int = 1) -> "MCMCSamples":
+        """Drop the first `burn_in` steps and keep every `thin`-th of the rest; the metadata accumulate (thin multiplies,
+        burn_in adds).  Nothing to do returns this object itself."""
+        if burn_in < 0:
+            raise ValueError("burn_in must be non-negative")
+        if thin <= 0:
+            raise ValueError("thin must be a positive integer")
+        if burn_in == 0 and thin == 1:
+            logger.warning("No burn-in or thinning applied, returning original samples")
+            return self
+        keep = slice(burn_in, None, thin)
+        chain = self.chain[keep]
+        per_row = lambda v: None if v is None else v.reshape(self.chain_shape)[keep].reshape(-1)  # noqa: E731
+        return self.__class__(x=chain.reshape(-1, self.dims), log_likelihood=per_row(self.log_likelihood),
+                              log_prior=per_row(self.log_prior), log_q=per_row(self.log_q), parameters=self.parameters, xp=self.xp,
+                              device=self.device, dtype=self.dtype, chain_shape=tuple(chain.shape[:-1]),
+                              thin=thin if self.thin is None else self.thin * thin,
+                              burn_in=burn_in if self.burn_in is None else self.burn_in + burn_in,
+                              autocorrelation_time=self.autocorrelation_time)
+
+    def __getitem__(self, idx):
+        sliced = super().__getitem__(idx)  # (chain_shape = None: the rows left are one flat chain)
+        sliced.thin, sliced.burn_in, sliced.autocorrelation_time = self.thin, self.burn_in, self.autocorrelation_time
+        return sliced
+
+    def to_numpy(self):
+        conv = lambda v: None if v is None else to_numpy(v)  # noqa: E731
+        return self.__class__(x=to_numpy(self.x), parameters=self.parameters, log_likelihood=conv(self.log_likelihood),
+                              log_prior=conv(self.log_prior), log_q=conv(self.log_q), xp=np, chain_shape=self.chain_shape,
+                              thin=self.thin, burn_in=self.burn_in, autocorrelation_time=conv(self.autocorrelation_time))
+
+    def to_namespace(self, xp, dtype=None):
+        dev = self.device if is_torch_namespace(xp) else None
+        conv = lambda v: None if v is None else asarray(v, xp, device=dev)  # noqa: E731
+        return self.__class__(x=conv(self.x), parameters=self.parameters, log_likelihood=conv(self.log_likelihood),
+                              log_prior=conv(self.log_prior), log_q=conv(self.log_q), xp=xp, dtype=dtype, chain_shape=self.chain_shape,
+                              **self._meta())
+
+    def _encode_for_hdf5(self, flat: bool = True) -> dict:
+        d = super()._encode_for_hdf5(flat=flat)
+        d["chain_shape"] = np.asarray(self.chain_shape, dtype=np.int64)  # (a tuple of ints has no dataset form of its own)
+        if d.get("autocorrelation_time") is not None:
+            d["autocorrelation_time"] = to_numpy(d["autocorrelation_time"])
+        return d
+
+
+@dataclass
 class SMCSamples(BaseSamples):
     """samples.py:1208-1332 — tempered particle population; the arithmetic runs in the engine."""
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 27
+#define ASMC_ABI_VERSION 28
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -938,6 +938,51 @@ int asmc_nuts_merge(asmc_ctx* ctx, const asmc_nuts_state* state, int doubling, u
                     int64_t* building_host, asmc_stream stream);
 int asmc_nuts_finish(asmc_ctx* ctx, const asmc_nuts_state* state, int x_dtype, void* x_dev, double* ll_dev, double* lp_dev,
                      double* lq_dev, int t, int* info_out_dev, asmc_stream stream);
+
+/* ---- chain recorder of the "minipcn" / "emcee" MCMC samplers (ABI 28) ------------------------------------------------------
+ * An MCMC run keeps every step of every walker: a device chain x_dev [n_slots, n, pitch] of x_dtype (pitch >= d elements per
+ * row; the elements beyond d are never written) with the carried log-likelihood / log-prior in ll_dev / lp_dev [n_slots, n]
+ * (fp64; either may be NULL).  Rows are always in x space.  Slot offsets are 64-bit.  No atomics; rows are written once.
+ * asmc_chain_record writes the walkers' current state into slot `slot` from one of two sources:
+ *   ASMC_CHAIN_ROWS  row-major src_dev [n, d] of the chain's dtype with its carried ll_src_dev / lp_src_dev: a copy (whole rows
+ *                    as 16-byte vectors where d * sizeof(T), the pitch and both pointers allow it).  With `t` the rows are
+ *                    z = T(x) and slot <- T^-1(z) by asmc_transform_inverse's kernels (pitch == d then).
+ *   ASMC_CHAIN_YS    the whitened coordinate-major state of the open asmc_pcn_ysplit_* session (`params`: the session's):
+ *                    slot <- mu + L y by the launch asmc_pcn_ysplit_end makes, pointed at the slot (pitch == d): the row is what
+ *                    ending the session at this step would return, bit for bit, and the state is only read.  src_dev is ignored.
+ * asmc_chain_set / asmc_chain_clear: a target the step loop INSIDE asmc_pcn_mutate honours - after step t of a call (t = 0 ..
+ * n_steps - 1) with t % stride == stride - 1 it records into slot slot0 + t / stride, on every path of the call:
+ *   - where it steps on x itself, the row-major state and the carried densities;
+ *   - where it steps on a whitened state (coordinate-major or row-major register kernels, d = 64 / 128 on the matrix cores), its
+ *     own un-whitening epilogue - x = mu + L y rounded to the storage type, densities re-evaluated at the stored x - with the slot
+ *     and the slot's density rows as its outputs (an epilogue that works in place gets a copy of the state there first);
+ *   - where it runs on a zero-padded copy (any other d <= 128), the same into scratch rows of the padded width, un-padded into
+ *     the slot by the kernel that un-pads the call's result.
+ * These are the launches that end a call of t + 1 steps: the slot holds what that call returns, bit for bit, and the state is only
+ * read.  asmc_pcn_mutate_flow does not record (an MCMC target has no proposal-density term) and returns ASMC_ERR_UNSUPPORTED
+ * while a target is set.  With no target set nothing differs from ABI 27.  The caller advances slot0 between calls.
+ * asmc_chain_set allocates its scratch in the context (n doubles, and n padded rows where d is zero-padded), not on a launch path;
+ * the target's pitch is d, and its x_dev 16-byte aligned where d is 4, 8, 16, 32, 64 or 128. */
+#define ASMC_CHAIN_ROWS 0
+#define ASMC_CHAIN_YS 1
+typedef struct asmc_chain_target {
+    void* x_dev;       /* [n_slots, n, pitch] */
+    double* ll_dev;    /* [n_slots, n] or NULL */
+    double* lp_dev;    /* [n_slots, n] or NULL */
+    int64_t n_slots;
+    int64_t n;         /* walkers */
+    int64_t pitch;     /* elements from one row to the next (>= d) */
+    int64_t slot0;     /* asmc_chain_set: slot of the first recorded step */
+    int32_t d;
+    int32_t x_dtype;   /* ASMC_F64 | ASMC_F32 */
+    int32_t stride;    /* asmc_chain_set: record every stride-th step (>= 1) */
+    int32_t reserved;
+} asmc_chain_target;
+int asmc_chain_record(asmc_ctx* ctx, const asmc_chain_target* chain, int64_t slot, int source, const void* src_dev,
+                      const double* ll_src_dev, const double* lp_src_dev, const asmc_pcn_params* params, const asmc_transform* t,
+                      asmc_stream stream);
+int asmc_chain_set(asmc_ctx* ctx, const asmc_chain_target* chain);
+int asmc_chain_clear(asmc_ctx* ctx);
 
 #ifdef __cplusplus
 }
