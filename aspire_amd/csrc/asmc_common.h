@@ -11,6 +11,7 @@
 #define ASMC_BLOCK 256          // 4 waves: one per SIMD of a CU
 #define ASMC_MAX_BLOCKS 2048    // cap for grid-stride reduction kernels (256 CUs x 8)
 #define ASMC_SCAN_TILE 2048     // elements per scan tile (256 threads x 8)
+#define SC_E (ASMC_SCAN_TILE / ASMC_BLOCK)  // ... per thread
 #define ASMC_PCN_MAX_GRID (1 << 20)  // blocks per pCN launch (>= 64 particles each): up to 67M particles per rank
 #define ASMC_GAMMA_BATCH 8       // Markov steps whose tpCN scale variates one k_gamma_draw launch draws (ctx->d_gamma holds that many)
 #define ASMC_MAX_PCN_STEPS 2048 // per asmc_pcn_mutate call (bounded by the pinned staging buffer)
@@ -82,10 +83,10 @@ struct asmc_ctx {
     int num_cu;
     // device scratch (all allocated in asmc_ctx_create)
     double* d_partials;            // [ASMC_MAX_BLOCKS * ASMC_MAX_BETAS * 2] block partial sums
-    double* d_small;               // [4096] small result vectors
+    double* d_small;               // [DS_LEN] small result vectors and state records (regions: asmc_scratch.h)
     unsigned long long* d_keys;    // [ASMC_MAX_BETAS + 8] atomicMax keys + integer counters
-    double* d_tiles;               // [n_tiles_max * 4 + 64] scan tile aggregates
-    long long* d_tiles_i;          // [n_tiles_max * 8 + 64] integer tile records (exact cdf: info + split; compaction)
+    double* d_tiles;               // [scratch_tiles_len] scan tile aggregates (asmc_scratch.h)
+    long long* d_tiles_i;          // [scratch_tiles_i_len] integer tile records (exact cdf: info + split; compaction)
     double* d_gram;                // [gram_blocks * d_max * d_max] gram partials
     unsigned int* d_guide;         // [n_max + 8] guide table of the resampling search (importance step: one bucket per cdf entry; asmc_search: one per four)
     unsigned char* d_flags;        // [n_max + 64] accept flags of the split-path pCN step (inside d_tilectr's allocation, behind the counters)
@@ -166,7 +167,7 @@ struct asmc_ctx {
     const void* prof_vfn[ASMC_PROF_VARIANTS];   // their host-side kernel handles
     long long prof_vcnt[ASMC_PROF_VARIANTS];    // and launches
     // pinned host staging for scalar read-back / small uploads
-    double* h_pinned;  // [8192] doubles
+    double* h_pinned;  // [HP_LEN] doubles (regions: asmc_scratch.h)
     unsigned ref_status_gen;  // asmc_reference_factor: generation of the pinned status cell in use (asmc_moments.hip)
     double* h_gram;    // [128 + 128 * 128] doubles: asmc_mean_gram's results (sum | Gram) until asmc_mean_gram_fetch
     double* d_ref;     // the same on the device (d_small / d_partials are every other call's scratch): asmc_reference_factor
@@ -179,6 +180,9 @@ struct asmc_ctx {
     void* d_chain_rows;            // [chain_rows_bytes] n rows of the padded width: where a zero-padded call un-whitens for the recorder
     size_t chain_rows_bytes;
 };
+#include "asmc_scratch.h"
+
+static inline int64_t scan_tiles(int64_t n) { return (n + ASMC_SCAN_TILE - 1) / ASMC_SCAN_TILE; }
 
 // asmc_chain.hip: rows [n, d] of src (row-major, x_dtype) and their carried densities -> slot `slot` of the chain
 int asmc_chain_rows_launch(asmc_ctx* ctx, const asmc_chain_target* c, int64_t slot, const void* src, const double* ll,
@@ -207,15 +211,32 @@ int asmc_flow16_sample(asmc_ctx* ctx, int64_t n, int x_dtype, const asmc_couplin
 bool asmc_pcn_flow16_ok(const asmc_pcn_params* prm, const asmc_coupling* f);
 bool asmc_flow_math_split();
 
-// asmc_weights.hip: the persistent weight kernel of asmc_importance_step (results in ctx->d_small + 2560 .. + 48)
 // k_ref_factor on the stream (asmc_moments.hip; asmc_reference_factor and the Student-t EM of asmc_student.hip)
 int asmc_ref_factor_launch(asmc_ctx* ctx, int d, const double* sum, const double* gram, double n_mean, double denom, double* out,
                            double* status, double* tab, double* em, int it, hipStream_t st);
 int asmc_gram_mm_launch(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, const double* d_center, int* grid_out,
                         hipStream_t st, double* out2, double n_div);
 bool asmc_gram_mm_supported(int d, const void* x);
+// asmc_weights.hip: the persistent weight kernel of asmc_importance_step (results in the first 48 doubles of DS_BISECT)
 int asmc_is_weights_launch(asmc_ctx* ctx, int64_t n, const double* ll, const double* lp, const double* lq, double beta0,
                            double target_eff, double tol, double* w, double* tiles, double* rec, hipStream_t st);
+// asmc_cdf.hip: the passes of the exact cdf of w [n] on the stream.
+//   prefixes  where a tile's approximate incoming sum comes from: XCDF_SUM_SCAN - k_tile_sum and k_scan_tiles;
+//             XCDF_HAVE_SUMS - ctx->d_tiles holds the tile sums already (k_is_weights): up to 1024 tiles the transducer pass
+//             adds them up itself (k_exact_tile_td_scan), above that k_scan_tiles runs
+//   carry / carry_dev  running sum in front of w[0], as a host value plus (if not NULL) a device value
+//   first_exact  tile 0 enters with exactly `carry` and is scanned element-wise by the transducer pass
+//   rec_pk    NULL: tile records in the context's tile arrays, then the sequential chain and the write pass - the cdf is
+//             complete, its total in DS_CDF_TOTAL; else: packed records [n_tiles][ASMC_CDF_REC] of the sharded scan, which
+//             chains all ranks' records itself: nothing follows the transducer pass
+//   norm      write pass: divide by *norm (NULL: leave the sums)      guide, nb: write pass: fill the search's guide table
+enum { XCDF_SUM_SCAN, XCDF_HAVE_SUMS };
+int asmc_exact_cdf_enqueue(asmc_ctx* ctx, int64_t n, const double* w, double* cdf, int prefixes, double carry, const double* carry_dev,
+                           int first_exact, long long* rec_pk, const double* norm, unsigned int* guide, int64_t nb, hipStream_t st);
+// asmc_resample.hip: range selection of the one-chain sharded step - count (every block forms the slice's edges itself and
+// block 0 leaves them in edges_out[4]), then scan + scatter + info in one launch
+int asmc_range_select_shard_launch(asmc_ctx* ctx, int64_t n_u, const double* u_dev, const double* state_dev, const double* s_in,
+                                   const double* cdf_last, double* edges_out_dev, double* out_dev, int64_t* info_dev, hipStream_t st);
 
 static inline hipStream_t as_stream(asmc_stream s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -178,7 +178,7 @@ int asmc_ctx_create(asmc_ctx** ctx_out, int device, int64_t n_max, int d_max) {
     c->n_max = n_max;
     c->d_max = d_max;
     c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    c->n_tiles_max = (n_max + ASMC_SCAN_TILE - 1) / ASMC_SCAN_TILE + 1;
+    c->n_tiles_max = scan_tiles(n_max) + 1;
     c->gram_blocks = (d_max <= 128 ? 4 : 2) * c->num_cu;  // partial matrices of the moment kernels (d_max^2 doubles each)
     if (c->gram_blocks > ASMC_MAX_BLOCKS) c->gram_blocks = ASMC_MAX_BLOCKS;
     hipError_t e = hipSuccess;
@@ -186,10 +186,10 @@ int asmc_ctx_create(asmc_ctx** ctx_out, int device, int64_t n_max, int d_max) {
         if (e == hipSuccess) e = hipMalloc(p, bytes);
     };
     dmalloc((void**)&c->d_partials, sizeof(double) * ASMC_MAX_BLOCKS * ASMC_MAX_BETAS * 2);
-    dmalloc((void**)&c->d_small, sizeof(double) * 4096);
+    dmalloc((void**)&c->d_small, sizeof(double) * DS_LEN);
     dmalloc((void**)&c->d_keys, sizeof(unsigned long long) * (ASMC_MAX_BETAS + 8));
-    dmalloc((void**)&c->d_tiles, sizeof(double) * (size_t)(c->n_tiles_max * 4 + 64));
-    dmalloc((void**)&c->d_tiles_i, sizeof(long long) * (size_t)(c->n_tiles_max * 8 + 64));
+    dmalloc((void**)&c->d_tiles, sizeof(double) * scratch_tiles_len(c->n_tiles_max));
+    dmalloc((void**)&c->d_tiles_i, sizeof(long long) * scratch_tiles_i_len(c->n_tiles_max));
     c->gram_cap = (size_t)c->gram_blocks * d_max * d_max;
     if (c->gram_cap < (size_t)2048 * 1024) c->gram_cap = (size_t)2048 * 1024;
     dmalloc((void**)&c->d_gram, sizeof(double) * c->gram_cap);
@@ -227,7 +227,7 @@ int asmc_ctx_create(asmc_ctx** ctx_out, int device, int64_t n_max, int d_max) {
         asmc_bm_table_host(tab);
         e = hipMemcpy(c->d_bmtab, tab, sizeof(tab), hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_pinned, sizeof(double) * 8192, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_pinned, sizeof(double) * HP_LEN, hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_gram, sizeof(double) * (128 + 128 * 128), hipHostMallocDefault);
     if (e != hipSuccess) {
         asmc_set_error("asmc_ctx_create: allocation failed: %s", hipGetErrorString(e));

@@ -400,8 +400,7 @@ int asmc_mean_gram_fetch(asmc_ctx* ctx, int d, double* sum_host, double* gram_ho
 // host writes the "not yet known" sentinel into a cell that no copy still in flight targets - an earlier request's late copy
 // lands in its own cell and cannot be mistaken for this request's status.  (The ring is deeper than the requests a caller can
 // have in flight between two synchronisations: one per temperature.)
-#define REF_STATUS_CELL0 8010
-#define REF_STATUS_CELLS 16
+// (REF_STATUS_CELL0, REF_STATUS_CELLS: asmc_scratch.h)
 static int ref_status_request(asmc_ctx* ctx, const double* d_status, hipStream_t st) {
     ctx->ref_status_gen++;
     double* cell = ctx->h_pinned + REF_STATUS_CELL0 + ctx->ref_status_gen % REF_STATUS_CELLS;
@@ -451,7 +450,7 @@ int asmc_reference_factor(asmc_ctx* ctx, int d, int64_t n_mean, int64_t n_cov, c
         ASMC_REQUIRE(ctx->gram_pending_d == d, "no asmc_mean_gram_enqueue of this d is pending");
         ctx->gram_pending_d = 0;
     }
-    double* d_status = ctx->d_small + 2300;
+    double* d_status = ctx->d_small + DS_REF_STATUS;
     const int rc = asmc_ref_factor_launch(ctx, d, ctx->d_ref, ctx->d_ref + 128, (double)n_mean, (double)(n_cov - 1 > 1 ? n_cov - 1 : 1),
                                           out_dev, d_status, nullptr, nullptr, 0, st);
     if (rc) return rc;
@@ -495,7 +494,7 @@ int asmc_centered_gram_dev(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const v
         return ASMC_ERR_UNSUPPORTED;
     }
     hipStream_t st = as_stream(stream);
-    double* d_center = ctx->d_small + 2048;
+    double* d_center = ctx->d_small + DS_GRAM_CENTER;
     ASMC_LAUNCH(ctx, st, "k_center_from_sum", k_center_from_sum, dim3(1), dim3(128), 0, st, d, sum_dev, (double)n_mean, d_center);
     ASMC_LAUNCH_CHECK();
     int ggrid = 0;
@@ -512,7 +511,7 @@ int asmc_reference_factor_dev(asmc_ctx* ctx, int d, int64_t n_mean, int64_t n_co
     ASMC_REQUIRE(ctx && sum_dev && gram_dev && out_dev, "null pointer");
     ASMC_REQUIRE(d > 0 && d <= 128 && n_mean > 0 && n_cov > 0, "bad sizes (d <= 128)");
     hipStream_t st = as_stream(stream);
-    double* d_status = ctx->d_small + 2300;
+    double* d_status = ctx->d_small + DS_REF_STATUS;
     const int rc = asmc_ref_factor_launch(ctx, d, sum_dev, gram_dev, (double)n_mean, (double)(n_cov - 1 > 1 ? n_cov - 1 : 1), out_dev,
                                           d_status, nullptr, nullptr, 0, st);
     if (rc) return rc;
@@ -561,9 +560,9 @@ int asmc_centered_gram(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void*
     ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
     hipStream_t st = as_stream(stream);
     ASMC_HIP(hipStreamSynchronize(st));
-    memcpy(ctx->h_pinned + 2048, center_host, sizeof(double) * d);
-    double* d_center = ctx->d_small + 2048;
-    ASMC_HIP(hipMemcpyAsync(d_center, ctx->h_pinned + 2048, sizeof(double) * d, hipMemcpyHostToDevice, st));
+    memcpy(ctx->h_pinned + HP_GRAM_CENTER, center_host, sizeof(double) * d);
+    double* d_center = ctx->d_small + DS_GRAM_CENTER;
+    ASMC_HIP(hipMemcpyAsync(d_center, ctx->h_pinned + HP_GRAM_CENTER, sizeof(double) * d, hipMemcpyHostToDevice, st));
     const size_t elem = x_dtype == ASMC_F64 ? 8 : 4;
     const int rowbytes = (int)(d * elem);
     double* d_out = ctx->d_partials;
@@ -582,8 +581,8 @@ int asmc_centered_gram(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void*
         if (D > 0 && D != d && D <= (ctx->d_max_pad < 32 ? 32 : ctx->d_max_pad) && !getenv("ASMC_GRAM_GENERIC") && !pcn_env_nopad()) {
             int rc = pcn_xpad_reserve(ctx, (size_t)n * D * elem, st, "centered_gram: no device memory for the zero-padded copy of the rows");
             if (rc) return rc;
-            for (int j = d; j < D; j++) ctx->h_pinned[2048 + j] = 0.0;
-            ASMC_HIP(hipMemcpyAsync(d_center, ctx->h_pinned + 2048, sizeof(double) * D, hipMemcpyHostToDevice, st));
+            for (int j = d; j < D; j++) ctx->h_pinned[HP_GRAM_CENTER + j] = 0.0;
+            ASMC_HIP(hipMemcpyAsync(d_center, ctx->h_pinned + HP_GRAM_CENTER, sizeof(double) * D, hipMemcpyHostToDevice, st));
             rc = launch_pad_rows(ctx, n, d, D, x_dtype, x, ctx->d_xpad, st);
             if (rc) return rc;
             int grid = 0;

@@ -677,8 +677,7 @@ __global__ __launch_bounds__(ASMC_BLOCK, 2) void k_pcn_reg(int64_t n, T* __restr
 // packed table of the transform epilogue: TRTAB_ROWS rows of D doubles, then TRTAB_SCALARS scalars
 //   rows: kind, lower, upper, mean, std, 1/(upper-lower), 1/std, premap a, b, lo, hi, h, q mean, q precision
 //   scalars: eps, unit_logj, affine_logj, has_affine, q log-weight, has_q, minus_logj
-#define TRTAB_ROWS 14
-#define TRTAB_SCALARS 8
+// (TRTAB_ROWS, TRTAB_SCALARS: asmc_scratch.h, with the table's place in the context's scratch)
 
 template <typename T, int D, int NOISE, int MODE>
 __global__ __launch_bounds__(ASMC_BLOCK, 2) void k_pcn_reg_flow(
@@ -1590,12 +1589,41 @@ int asmc_pcn_set_count_cells(asmc_ctx* ctx, int n_cells) {
 
 // The reference checks the carried log q for NaN after every mutation (smc/minipcn.py: "Log proposal contains NaN values").
 // The count rides on the mutation call's own read-back instead of a call and a synchronisation of its own: NaN / inf counts
-// of lq -> h_pinned[8002 .. 8003], read by asmc_pcn_lq_nan after the call's synchronisation.
+// of lq -> HP_PCN_LQ_COUNTS, read by asmc_pcn_lq_nan after the call's synchronisation.
 static int pcn_enqueue_lq_check(asmc_ctx* ctx, int64_t n, const double* lq, hipStream_t st) {
     const int rc = asmc_count_nonfinite_enqueue(ctx, n, lq, st);
     if (rc) return rc;
-    ASMC_HIP(hipMemcpyAsync(ctx->h_pinned + 8002, asmc_count_slot(ctx), sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, st));
+    ASMC_HIP(hipMemcpyAsync(ctx->h_pinned + HP_PCN_LQ_COUNTS, asmc_count_slot(ctx), sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, st));
     return ASMC_OK;
+}
+
+// A mutation call's read-back into the pinned HP_PCN_* cells (asmc_scratch.h): accept counts | step sizes | rho.
+// d_bad == NULL: counts, history and rho (-> HP_PCN_RHO) in a copy each.  Flow steps pass their non-finite-density counter: d_rho's
+// head and the history then come in ONE copy (d_rho_hist = d_rho + 8: rho lands in HP_PCN_RHO_HEAD) and *d_bad -> HP_PCN_NONFINITE.
+static int pcn_readback_enqueue(asmc_ctx* ctx, int n_steps, const void* d_bad, hipStream_t st) {
+    double* h = ctx->h_pinned;
+    ASMC_HIP(hipMemcpyAsync(h + HP_PCN_COUNTS, ctx->d_counts, sizeof(long long) * n_steps, hipMemcpyDeviceToHost, st));
+    if (!d_bad) {
+        ASMC_HIP(hipMemcpyAsync(h + HP_PCN_RHO_HIST, ctx->d_rho + 8, sizeof(double) * n_steps, hipMemcpyDeviceToHost, st));
+        ASMC_HIP(hipMemcpyAsync(h + HP_PCN_RHO, ctx->d_rho, sizeof(double), hipMemcpyDeviceToHost, st));
+    } else {
+        ASMC_HIP(hipMemcpyAsync(h + HP_PCN_RHO_HEAD, ctx->d_rho, sizeof(double) * (8 + n_steps), hipMemcpyDeviceToHost, st));
+        ASMC_HIP(hipMemcpyAsync(h + HP_PCN_NONFINITE, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    }
+    return ASMC_OK;
+}
+// ... handed out once the caller has waited for it.  flow: pcn_readback_enqueue had a d_bad; lq_checked: pcn_enqueue_lq_check
+// followed it
+static void pcn_readback_handout(asmc_ctx* ctx, int n_steps, bool flow, bool lq_checked, double* rho_out_host, int64_t* n_accept_host,
+                                 double* rho_hist_host) {
+    const long long* h_counts = reinterpret_cast<const long long*>(ctx->h_pinned + HP_PCN_COUNTS);
+    const double* h_rho_hist = ctx->h_pinned + HP_PCN_RHO_HIST;
+    if (lq_checked) memcpy(&ctx->lq_nan, ctx->h_pinned + HP_PCN_LQ_COUNTS, sizeof(unsigned long long));
+    for (int t = 0; t < n_steps; t++) n_accept_host[t] = (int64_t)h_counts[t];
+    if (rho_hist_host)
+        for (int t = 0; t < n_steps; t++) rho_hist_host[t] = h_rho_hist[t];
+    *rho_out_host = ctx->h_pinned[flow ? HP_PCN_RHO_HEAD : HP_PCN_RHO];
+    if (flow) memcpy(&ctx->flow_nonfinite, ctx->h_pinned + HP_PCN_NONFINITE, sizeof(unsigned long long));  // fused steps only (else stale zero)
 }
 
 // the exchange issued by the library: RCCL's all-reduce on the step kernels' own stream (include/asmc.h)
@@ -1727,7 +1755,7 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
     const double t_a = now();
     ASMC_HIP(hipStreamSynchronize(st));
     const double t_b = now();
-    ctx->h_pinned[0] = *rho_inout_host;
+    ctx->h_pinned[HP_FRONT] = *rho_inout_host;
     ASMC_HIP(hipMemcpyAsync(d_rho, ctx->h_pinned, sizeof(double), hipMemcpyHostToDevice, st));
     // Slot of step t of this call (asmc_chain_set).  Not whitened: the rows are x itself (un-padded on their way when the call
     // runs on a zero-padded copy).  Whitened: the call's own un-whitening launch `unwhiten(rec)` with the slot's rows (the padded
@@ -1775,19 +1803,12 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
         }
         rc = asmc_pcn_mm_launch(ctx, n, prm->x_dtype, x, ll, lp, lq, pd, MM_UNWHITEN, d_rho, 0, d_block, &grid, st);
         if (rc) return rc;
-        long long* h_counts = reinterpret_cast<long long*>(ctx->h_pinned);
-        double* h_rho_hist = ctx->h_pinned + ASMC_MAX_PCN_STEPS + 8;
-        ASMC_HIP(hipMemcpyAsync(h_counts, d_counts, sizeof(long long) * n_steps, hipMemcpyDeviceToHost, st));
-        ASMC_HIP(hipMemcpyAsync(h_rho_hist, d_rho_hist, sizeof(double) * n_steps, hipMemcpyDeviceToHost, st));
-        ASMC_HIP(hipMemcpyAsync(ctx->h_pinned + 8000, d_rho, sizeof(double), hipMemcpyDeviceToHost, st));
+        rc = pcn_readback_enqueue(ctx, n_steps, nullptr, st);
+        if (rc) return rc;
         rc = pcn_enqueue_lq_check(ctx, n, lq, st);
         if (rc) return rc;
         ASMC_HIP(hipStreamSynchronize(st));
-        for (int t = 0; t < n_steps; t++) n_accept_host[t] = (int64_t)h_counts[t];
-        if (rho_hist_host)
-            for (int t = 0; t < n_steps; t++) rho_hist_host[t] = h_rho_hist[t];
-        *rho_inout_host = ctx->h_pinned[8000];
-        memcpy(&ctx->lq_nan, ctx->h_pinned + 8002, sizeof(unsigned long long));
+        pcn_readback_handout(ctx, n_steps, false, true, rho_inout_host, n_accept_host, rho_hist_host);
         return ASMC_OK;
     }
     const bool reg_ok = pcn_reg_supported(pd.d, prm->x_dtype == ASMC_F64 ? 8 : 4, x);
@@ -1850,20 +1871,13 @@ static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double
     }
     const double t_c = now();
     // read back: counts [n_steps] | rho_hist [n_steps] | rho
-    long long* h_counts = reinterpret_cast<long long*>(ctx->h_pinned);
-    double* h_rho_hist = ctx->h_pinned + ASMC_MAX_PCN_STEPS + 8;  // disjoint from the counts
-    ASMC_HIP(hipMemcpyAsync(h_counts, d_counts, sizeof(long long) * n_steps, hipMemcpyDeviceToHost, st));
-    ASMC_HIP(hipMemcpyAsync(h_rho_hist, d_rho_hist, sizeof(double) * n_steps, hipMemcpyDeviceToHost, st));
-    ASMC_HIP(hipMemcpyAsync(ctx->h_pinned + 8000, d_rho, sizeof(double), hipMemcpyDeviceToHost, st));
+    rc = pcn_readback_enqueue(ctx, n_steps, nullptr, st);
+    if (rc) return rc;
     rc = pcn_enqueue_lq_check(ctx, n, lq, st);
     if (rc) return rc;
     ASMC_HIP(hipStreamSynchronize(st));
-    memcpy(&ctx->lq_nan, ctx->h_pinned + 8002, sizeof(unsigned long long));
     if (dbg) fprintf(stderr, "[asmc_pcn_mutate] sync0 %.3f ms, enqueue %.3f ms, drain %.3f ms (n_steps=%d)\n", t_b - t_a, t_c - t_b, now() - t_c, n_steps);
-    for (int t = 0; t < n_steps; t++) n_accept_host[t] = (int64_t)h_counts[t];
-    if (rho_hist_host)
-        for (int t = 0; t < n_steps; t++) rho_hist_host[t] = h_rho_hist[t];
-    *rho_inout_host = ctx->h_pinned[8000];
+    pcn_readback_handout(ctx, n_steps, false, true, rho_inout_host, n_accept_host, rho_hist_host);
     return ASMC_OK;
 }
 
@@ -1978,17 +1992,11 @@ int asmc_pcn_split_end(asmc_ctx* ctx, int n_steps, int64_t* n_accept_host, doubl
     ASMC_REQUIRE(ctx && n_accept_host && rho_host, "null pointer");
     ASMC_REQUIRE(n_steps >= 1 && n_steps <= ASMC_MAX_PCN_STEPS, "n_steps out of range");
     hipStream_t st = as_stream(stream);
-    long long* h_counts = reinterpret_cast<long long*>(ctx->h_pinned);
-    double* h_rho_hist = ctx->h_pinned + ASMC_MAX_PCN_STEPS + 8;
     ASMC_HIP(hipStreamSynchronize(st));  // pinned staging may still be in flight
-    ASMC_HIP(hipMemcpyAsync(h_counts, ctx->d_counts, sizeof(long long) * n_steps, hipMemcpyDeviceToHost, st));
-    ASMC_HIP(hipMemcpyAsync(h_rho_hist, ctx->d_rho + 8, sizeof(double) * n_steps, hipMemcpyDeviceToHost, st));
-    ASMC_HIP(hipMemcpyAsync(ctx->h_pinned + 8000, ctx->d_rho, sizeof(double), hipMemcpyDeviceToHost, st));
+    const int rc = pcn_readback_enqueue(ctx, n_steps, nullptr, st);
+    if (rc) return rc;
     ASMC_HIP(hipStreamSynchronize(st));
-    for (int t = 0; t < n_steps; t++) n_accept_host[t] = (int64_t)h_counts[t];
-    if (rho_hist_host)
-        for (int t = 0; t < n_steps; t++) rho_hist_host[t] = h_rho_hist[t];
-    *rho_host = ctx->h_pinned[8000];
+    pcn_readback_handout(ctx, n_steps, false, false, rho_host, n_accept_host, rho_hist_host);
     return ASMC_OK;
 }
 
@@ -2115,7 +2123,7 @@ int asmc_pcn_ysplit_propose_tr(asmc_ctx* ctx, int64_t n, const asmc_pcn_params* 
     }
     rc = pcn_prepare_gamma(ctx, n, pd, step, st);
     if (rc) return rc;
-    double* d_tab = ctx->d_small + 3072;  // TRTAB_ROWS * 32 + TRTAB_SCALARS doubles
+    double* d_tab = ctx->d_small + DS_TRTAB;  // DS_TRTAB_LEN doubles
     ASMC_LAUNCH(ctx, st, "k_trtab_pack", k_trtab_pack, dim3(1), dim3(64), 0, st, pd.d, t->kind_dev, t->lower_dev, t->upper_dev,
                 t->mean_dev, t->std_dev, premap_dev, qmix ? qmix->logw_dev : (const double*)nullptr,
                 qmix ? qmix->mu_dev : (const double*)nullptr, qmix ? qmix->prec_dev : (const double*)nullptr, t->eps, t->unit_logj,
@@ -2242,18 +2250,11 @@ int64_t asmc_pcn_flow_work_bytes(int64_t n, int d, int x_dtype) {
 // waits for a flow-mutation call's read-back (counts | step sizes | rho | non-finite count | NaNs of log q) and hands it out
 static int mutate_flow_collect(asmc_ctx* ctx, int n_steps, double* rho_out_host, int64_t* n_accept_host, double* rho_hist_host,
                                hipStream_t st, hipEvent_t ev = nullptr) {
-    const long long* h_counts = reinterpret_cast<const long long*>(ctx->h_pinned);
-    const double* h_rho_hist = ctx->h_pinned + ASMC_MAX_PCN_STEPS + 8;
     if (ev)
         ASMC_HIP(hipEventSynchronize(ev));
     else
         ASMC_HIP(hipStreamSynchronize(st));
-    memcpy(&ctx->lq_nan, ctx->h_pinned + 8002, sizeof(unsigned long long));
-    for (int t = 0; t < n_steps; t++) n_accept_host[t] = (int64_t)h_counts[t];
-    if (rho_hist_host)
-        for (int t = 0; t < n_steps; t++) rho_hist_host[t] = h_rho_hist[t];
-    *rho_out_host = h_rho_hist[-8];
-    memcpy(&ctx->flow_nonfinite, ctx->h_pinned + 8001, sizeof(unsigned long long));  // fused steps only (else stale zero)
+    pcn_readback_handout(ctx, n_steps, true, true, rho_out_host, n_accept_host, rho_hist_host);
     return ASMC_OK;
 }
 
@@ -2429,13 +2430,8 @@ static int pcn_mutate_flow_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, d
         rc = pcn_close_step(ctx, st, 1, (const long long*)d_cnt, n, t, d_counts, d_rho, d_rho_hist, prm->target_accept, prm->adapt, t == n_steps - 1);
         if (rc) return rc;
     }
-    long long* h_counts = reinterpret_cast<long long*>(ctx->h_pinned);
-    double* h_rho_hist = ctx->h_pinned + ASMC_MAX_PCN_STEPS + 8;
-    ASMC_HIP(hipMemcpyAsync(h_counts, d_counts, sizeof(long long) * n_steps, hipMemcpyDeviceToHost, st));
-    // the step size and its history in one copy (d_rho_hist = d_rho + 8): rho lands at h_rho_hist[-8]
-    ASMC_HIP(hipMemcpyAsync(h_rho_hist - 8, d_rho, sizeof(double) * (8 + n_steps), hipMemcpyDeviceToHost, st));
-    ASMC_HIP(hipMemcpyAsync(ctx->h_pinned + 8001, ctx->d_tilectr + 2 * ASMC_MAX_PCN_STEPS, sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, st));
+    rc = pcn_readback_enqueue(ctx, n_steps, ctx->d_tilectr + 2 * ASMC_MAX_PCN_STEPS, st);
+    if (rc) return rc;
     rc = pcn_enqueue_lq_check(ctx, n, lq, st);
     if (rc) return rc;
     if (ctx->mutate_defer) {  // asmc_pcn_mutate_flow_enqueue: the results wait in pinned memory for asmc_pcn_mutate_flow_result
@@ -2494,11 +2490,8 @@ static int pcn_mutate_flow16_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll,
     }
     rc = asmc_pcn_mm_launch(ctx, n, prm->x_dtype, x, ll, lp, lq, pd, MM_UNWHITEN_X, d_rho, 0, d_block, &grid, st);
     if (rc) return rc;
-    long long* h_counts = reinterpret_cast<long long*>(ctx->h_pinned);
-    double* h_rho_hist = ctx->h_pinned + ASMC_MAX_PCN_STEPS + 8;
-    ASMC_HIP(hipMemcpyAsync(h_counts, d_counts, sizeof(long long) * n_steps, hipMemcpyDeviceToHost, st));
-    ASMC_HIP(hipMemcpyAsync(h_rho_hist - 8, d_rho, sizeof(double) * (8 + n_steps), hipMemcpyDeviceToHost, st));
-    ASMC_HIP(hipMemcpyAsync(ctx->h_pinned + 8001, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    rc = pcn_readback_enqueue(ctx, n_steps, d_bad, st);
+    if (rc) return rc;
     rc = pcn_enqueue_lq_check(ctx, n, lq, st);
     if (rc) return rc;
     if (ctx->mutate_defer) {

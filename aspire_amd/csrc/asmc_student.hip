@@ -246,8 +246,8 @@ int asmc_student_fit(asmc_ctx* ctx, int64_t m, int d, const double* xs, int max_
     const int blocks = (int)((m + ST_ROWS - 1) / ST_ROWS);
     double* d_tab = ctx->d_student;
     double* d_part = ctx->d_student + (size_t)ctx->d_max * (ctx->d_max + 1);
-    double* d_em = ctx->d_small + 2320;  // 8 doubles
-    double* d_zero = ctx->d_small + 2048;  // the Gram kernel's centre
+    double* d_em = ctx->d_small + DS_STUDENT_EM;
+    double* d_zero = ctx->d_small + DS_GRAM_CENTER;  // the Gram kernel's centre
     double* h = ctx->h_student;
     ASMC_HIP(hipStreamSynchronize(st));  // pinned staging may still be in flight from an earlier call
     h[0] = nu0, h[1] = 0.0, h[2] = 1e9, h[3] = 0.0, h[4] = rtol, h[5] = h[6] = h[7] = 0.0;
@@ -286,7 +286,7 @@ int asmc_student_fit(asmc_ctx* ctx, int64_t m, int d, const double* xs, int max_
         ASMC_LAUNCH_CHECK();
     }
     // the final fit's factor and inverse for the mutation (mu from the table: sum = mu, n_mean = 1; Sigma = scatter / m)
-    double* d_status = ctx->d_small + 2300;
+    double* d_status = ctx->d_small + DS_REF_STATUS;
     rc = asmc_ref_factor_launch(ctx, d, d_tab, ctx->d_ref + 128, 1.0, (double)m, out_dev, d_status, nullptr, nullptr, 0, st);
     if (rc) return rc;
     ASMC_HIP(hipMemcpyAsync(h, d_em, sizeof(double) * 8, hipMemcpyDeviceToHost, st));

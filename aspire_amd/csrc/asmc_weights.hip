@@ -333,7 +333,7 @@ static int check_common(asmc_ctx* ctx, int64_t n, const void* a, const void* b, 
 
 // ---------------------------------------------------------------------------------------------
 // Device-side k-ary bisection (smc/base.py:167-186): the whole adaptive-beta search runs as a chain of
-// launches without host round trips.  State (doubles) in ctx->d_small + 2048:
+// launches without host round trips.  State (doubles) in ctx->d_small + DS_BISECT (asmc_scratch.h):
 //   [0] beta_min  [1] beta_max  [2] done  [3] target_eff  [4] tol  [5] log N  [6] n_pass  [7] beta0
 //   [8] N  [9] ESS(1)/N  [16..27] bracket and next grid as dyadic node indices (asmc_bisect.h)
 #define BIS_LEVELS 4
@@ -1322,8 +1322,8 @@ int asmc_find_beta(asmc_ctx* ctx, int64_t n, const double* ll, const double* lp,
     ASMC_REQUIRE(out_host != nullptr, "null host pointer");
     ASMC_REQUIRE(tol > 0.0 && beta0 >= 0.0 && beta0 < 1.0, "bad beta0 / tolerance");
     hipStream_t st = as_stream(stream);
-    double* d_st = ctx->d_small + 2560;
-    double* h = ctx->h_pinned + 4096 + 512;
+    double* d_st = ctx->d_small + DS_BISECT;
+    double* h = ctx->h_pinned + HP_STEP_RESULT;
     const BisInit init = {beta0, target_eff, tol, log((double)n), (double)n, bis_plain_mode()};
     // exact maximum at beta = 1 (also the NaN census: for beta > beta0 the NaN pattern of the log-weights does not
     // depend on beta); every round, the first one included (it evaluates beta = 1 as its 16th candidate), is then ONE launch
@@ -1386,7 +1386,7 @@ int asmc_is_weights_launch(asmc_ctx* ctx, int64_t n, const double* ll, const dou
         chunk = (chunk + ISW_CHUNK - 1) / ISW_CHUNK * ISW_CHUNK;
         grid = (n + chunk - 1) / chunk;
     }
-    double* d_st = ctx->d_small + 2560;
+    double* d_st = ctx->d_small + DS_BISECT;
     IswBases bases;
     bases.top = ctx->bar_base[0];
     if (getenv("ASMC_ISW_TEST_TIMEOUT")) bases.top += 1000000u;  // test hook: the barriers of this launch can never complete
@@ -1420,9 +1420,9 @@ extern "C" {
 int asmc_importance_result_enqueue(asmc_ctx* ctx, asmc_stream stream) {
     ASMC_REQUIRE(ctx != nullptr, "null ctx");
     hipStream_t st = as_stream(stream);
-    double* h = ctx->h_pinned + 4096 + 512;
+    double* h = ctx->h_pinned + HP_STEP_RESULT;
     unsigned int* hp = reinterpret_cast<unsigned int*>(h + 64);
-    ASMC_HIP(hipMemcpyAsync(h, ctx->d_small + 2560, sizeof(double) * 64, hipMemcpyDeviceToHost, st));
+    ASMC_HIP(hipMemcpyAsync(h, ctx->d_small + DS_BISECT, sizeof(double) * 64, hipMemcpyDeviceToHost, st));
     ASMC_HIP(hipMemcpyAsync(hp, ctx->d_bar + ISW_POISON_CELL, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     if (!ctx->ev_is) ASMC_HIP(hipEventCreateWithFlags(&ctx->ev_is, hipEventDisableTiming));
     ASMC_HIP(hipEventRecord(ctx->ev_is, st));
@@ -1433,13 +1433,13 @@ int asmc_importance_result_enqueue(asmc_ctx* ctx, asmc_stream stream) {
 int asmc_importance_result(asmc_ctx* ctx, double* out_host, asmc_stream stream) {
     ASMC_REQUIRE(ctx && out_host, "null pointer");
     hipStream_t st = as_stream(stream);
-    double* h = ctx->h_pinned + 4096 + 512;
+    double* h = ctx->h_pinned + HP_STEP_RESULT;
     unsigned int* hp = reinterpret_cast<unsigned int*>(h + 64);
     if (ctx->is_result_pending) {  // asmc_importance_result_enqueue has put the copies on the stream already
         ctx->is_result_pending = 0;
         ASMC_HIP(hipEventSynchronize(ctx->ev_is));
     } else {
-        ASMC_HIP(hipMemcpyAsync(h, ctx->d_small + 2560, sizeof(double) * 64, hipMemcpyDeviceToHost, st));
+        ASMC_HIP(hipMemcpyAsync(h, ctx->d_small + DS_BISECT, sizeof(double) * 64, hipMemcpyDeviceToHost, st));
         ASMC_HIP(hipMemcpyAsync(hp, ctx->d_bar + ISW_POISON_CELL, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
         ASMC_HIP(hipStreamSynchronize(st));
     }
@@ -1472,14 +1472,14 @@ int asmc_importance_available(asmc_ctx* ctx) { return ctx && !ctx->isw_disabled 
 int asmc_importance_tile_sums(asmc_ctx* ctx, int64_t n, double* out_dev, asmc_stream stream) {
     ASMC_REQUIRE(ctx && out_dev, "null pointer");
     ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
-    const int64_t n_tiles = (n + ASMC_SCAN_TILE - 1) / ASMC_SCAN_TILE;
+    const int64_t n_tiles = scan_tiles(n);
     ASMC_REQUIRE(n_tiles <= 1024, "above 1024 tiles the scan overwrites the tile sums with their prefix");
     ASMC_HIP(hipMemcpyAsync(out_dev, ctx->d_tiles, sizeof(double) * (size_t)n_tiles, hipMemcpyDeviceToDevice, as_stream(stream)));
     return ASMC_OK;
 }
 
 static inline void bis_state(asmc_ctx* ctx, double** d_st, unsigned int** d_ticket) {
-    *d_st = ctx->d_small + 2560;
+    *d_st = ctx->d_small + DS_BISECT;
     *d_ticket = reinterpret_cast<unsigned int*>(ctx->d_keys + ASMC_MAX_BETAS + 4);  // zeroed by launch_max
 }
 
@@ -1548,8 +1548,8 @@ int asmc_find_beta_shard_rounds(asmc_ctx* ctx, int64_t n, const double* ll, cons
 int asmc_find_beta_shard_result(asmc_ctx* ctx, double* out_host, asmc_stream stream) {
     ASMC_REQUIRE(ctx && out_host, "null pointer");
     hipStream_t st = as_stream(stream);
-    double* h = ctx->h_pinned + 4096 + 512;
-    ASMC_HIP(hipMemcpyAsync(h, ctx->d_small + 2560, sizeof(double) * 40, hipMemcpyDeviceToHost, st));
+    double* h = ctx->h_pinned + HP_STEP_RESULT;
+    ASMC_HIP(hipMemcpyAsync(h, ctx->d_small + DS_BISECT, sizeof(double) * 40, hipMemcpyDeviceToHost, st));
     ASMC_HIP(hipStreamSynchronize(st));
     out_host[0] = h[0], out_host[1] = h[1], out_host[2] = h[2], out_host[3] = h[6], out_host[4] = h[9];
     out_host[5] = h[15];
@@ -1575,7 +1575,7 @@ int asmc_weights_m2(asmc_ctx* ctx, int64_t n, const double* ll, const double* lp
     ASMC_LAUNCH_CHECK();
     ASMC_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_small, sizeof(double), hipMemcpyDeviceToHost, st));
     ASMC_HIP(hipStreamSynchronize(st));
-    *m2_host = ctx->h_pinned[0];
+    *m2_host = ctx->h_pinned[HP_FRONT];
     return ASMC_OK;
 }
 
@@ -1595,8 +1595,8 @@ int asmc_weights_m2_lse(asmc_ctx* ctx, int64_t n, const double* ll, const double
     ASMC_LAUNCH_CHECK();
     ASMC_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_small, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
     ASMC_HIP(hipStreamSynchronize(st));
-    out_host[0] = ctx->h_pinned[0];
-    out_host[1] = ctx->h_pinned[1];
+    out_host[0] = ctx->h_pinned[HP_FRONT];
+    out_host[1] = ctx->h_pinned[HP_FRONT + 1];
     return ASMC_OK;
 }
 
@@ -1621,7 +1621,7 @@ int asmc_weights_m2_lse_dev(asmc_ctx* ctx, int64_t n, const double* ll, const do
 // stays where it is, these passes read it there.
 // state record S_r (after r closed rounds) of the folded sharded search: two buffers, S_r in buffer r & 1 - the kernel that
 // closes round r - 1 reads S_{r-1} while its block 0 writes S_r
-static inline double* shard_state_buf(asmc_ctx* ctx, int r) { return ctx->d_small + 2560 + ((r & 1) ? 64 : 0); }
+static inline double* shard_state_buf(asmc_ctx* ctx, int r) { return ctx->d_small + DS_BISECT + ((r & 1) ? DS_BISECT_REC : 0); }
 
 int asmc_find_beta_shard_round(asmc_ctx* ctx, int64_t n, const double* ll, const double* lp, const double* lq, double beta0,
                                double target_eff, double tol, int world, int64_t n_global, int round, const double* recs_prev_dev,
@@ -1686,7 +1686,7 @@ int asmc_normalized_weights_shard(asmc_ctx* ctx, int64_t n, const double* ll, co
     ASMC_REQUIRE(carry_uniform >= 0.0 && carry_uniform < 1.0, "bad uniform carry");
     ASMC_REQUIRE(ctx->shard_st != nullptr, "asmc_weights_m2_lse_shard first");
     hipStream_t st = as_stream(stream);
-    const int64_t n_tiles = (n + ASMC_SCAN_TILE - 1) / ASMC_SCAN_TILE;
+    const int64_t n_tiles = scan_tiles(n);
     ASMC_LAUNCH(ctx, st, "k_weights_map_shard", k_weights_map_shard, dim3((unsigned)n_tiles), dim3(ASMC_BLOCK), 0, st, n, ll, lp, lq,
                 (const double*)ctx->shard_st, parts_dev, world, rank, carry_uniform, w_out, carry_out_dev, tile_sums_dev, state_copy_dev,
                 pack_records ? ctx->d_rec : (double*)nullptr);
@@ -1706,7 +1706,7 @@ int asmc_shard_step_result(asmc_ctx* ctx, const double* res_dev, int world, doub
     ASMC_REQUIRE(ctx && res_dev && out_host, "null pointer");
     ASMC_REQUIRE(world >= 1 && world <= 64, "world out of range");
     hipStream_t st = as_stream(stream);
-    double* h = ctx->h_pinned + 4096 + 512;
+    double* h = ctx->h_pinned + HP_STEP_RESULT;
     ASMC_HIP(hipMemcpyAsync(h, res_dev, sizeof(double) * (40 + 4 * world), hipMemcpyDeviceToHost, st));
     ASMC_HIP(hipStreamSynchronize(st));
     out_host[0] = h[0], out_host[1] = h[1], out_host[2] = h[2], out_host[3] = h[6], out_host[4] = h[9];

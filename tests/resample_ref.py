@@ -1,4 +1,4 @@
-"""Plain restatement of the resampling operations of csrc/asmc_resample.hip (no GPU, nothing imported from the code under test):
+"""Plain restatement of the resampling operations of csrc/asmc_cdf.hip and csrc/asmc_resample.hip (no GPU, nothing imported from the code under test):
 the judge of tests/test_gpu_resample.py, pinned by tests/test_resample_ref.py.  DESIGN.md section 3.17 has the path table.
 
   exact cdf            np.cumsum (sequential fp64): the device must give its bits

@@ -1,4 +1,4 @@
-"""The resampling kernels of csrc/asmc_resample.hip on every dispatch path and at the edges, against the plain restatement of
+"""The resampling kernels of csrc/asmc_cdf.hip and csrc/asmc_resample.hip on every dispatch path and at the edges, against the plain restatement of
 tests/resample_ref.py (tolerance of the fast cdf: its docstring and DESIGN.md section 3.17; it does not come from the device's output).
 The exact cdf has its own bitwise tests (tests/test_gpu_parity.py); here it only serves as the cdf the searches run on.
 
@@ -581,9 +581,9 @@ def test_shard_finish_select_equals_finish_then_select(eng, n, cuts, n_u):
 
 # ---- every kernel of the families ran ---------------------------------------------------------------------------------------------------
 def test_every_kernel_symbol_ran():
-    """Closes the module: every __global__ kernel of csrc/asmc_resample.hip in the families above, in every instantiation the
+    """Closes the module: every __global__ kernel of csrc/asmc_cdf.hip and csrc/asmc_resample.hip in the families above, in every instantiation the
     library launches, appears in an asserted launch.  It needs the whole module to have run: under a -k selection it fails."""
-    src = open(os.path.join(ROOT, "aspire_amd", "csrc", "asmc_resample.hip")).read()
+    src = "".join(open(os.path.join(ROOT, "aspire_amd", "csrc", f)).read() for f in ("asmc_cdf.hip", "asmc_resample.hip"))
     kernels = set(re.findall(r"__global__\s+(?:__launch_bounds__\([A-Z_0-9a-z]+\)\s+)?void\s+(k_[a-z0-9_]+)\s*\(", src))
     kernels = {k for k in kernels if any(f in k for f in FAMILIES)}
     assert len(kernels) == 22, sorted(kernels)

@@ -5,15 +5,19 @@ Build each tree with the Makefile's flags plus -save-temps=obj into a directory 
     python3 tools/compare_device_code.py OLD_DIR NEW_DIR
 Every FUNC symbol's bytes and every kernel descriptor (<kernel>.kd, bytes 16..23 masked: the code-entry offset moves with
 the layout) of all *-gfx950.out device objects are compared by symbol name over the union of the translation units, so a
-kernel may move between files.  Exit status 0: same symbols, same bytes."""
+kernel may move between files.  Exit status 0: same symbols, same bytes.
+
+A kernel that calls a function the compiler did not inline (`s_getpc_b64` + `@rel32`) carries the distance to it in its linked
+bytes, and that distance changes when a kernel that lay between the two moves to another file.  `--relocatable` compares the
+*-gfx950.o objects instead, in which such a call is still a relocation: use it to tell a moved neighbour from changed code."""
 import glob, os, re, subprocess, sys
 
 READELF = os.environ.get("LLVM_READELF", "/opt/rocm/llvm/bin/llvm-readelf")
 
 
-def symbols(directory):
+def symbols(directory, suffix="-gfx950.out"):
     out, per_file = {}, {}
-    for path in sorted(glob.glob(os.path.join(directory, "*-gfx950.out"))):
+    for path in sorted(glob.glob(os.path.join(directory, "*" + suffix))):
         text = subprocess.run([READELF, "-sW", "-S", path], check=True, capture_output=True, text=True).stdout
         blob = open(path, "rb").read()
         sec = {int(m[1]): (int(m[2], 16), int(m[3], 16))  # index -> (address, file offset)
@@ -36,8 +40,8 @@ def symbols(directory):
     return out, per_file
 
 
-def main(old_dir, new_dir):
-    (old, old_files), (new, new_files) = symbols(old_dir), symbols(new_dir)
+def main(old_dir, new_dir, suffix="-gfx950.out"):
+    (old, old_files), (new, new_files) = symbols(old_dir, suffix), symbols(new_dir, suffix)
     for label, files in (("old", old_files), ("new", new_files)):
         print(f"{label}: " + ", ".join(f"{k} {v}" for k, v in files.items()))
     gone, added = sorted(set(old) - set(new)), sorted(set(new) - set(old))
@@ -51,4 +55,5 @@ def main(old_dir, new_dir):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    args = [a for a in sys.argv[1:] if a != "--relocatable"]
+    sys.exit(main(args[0], args[1], "-gfx950.o" if "--relocatable" in sys.argv else "-gfx950.out"))
