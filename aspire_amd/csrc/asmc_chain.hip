@@ -3,7 +3,7 @@
 // An MCMC run keeps every step of every walker in a device chain [n_slots, n, pitch].  A slot is written once, from
 //   - row-major rows (the generic pCN path, the stretch move, asmc_pcn_mutate where it steps on x): the copy kernel below, or
 //     asmc_transform_inverse's kernels with the slot as their output when the chain runs in z = T(x);
-//   - the whitened coordinate-major state of a session: the un-whitening launch of asmc_pcn_ysplit_end (asmc_pcn.hip) with the
+//   - the whitened coordinate-major state of a session: the un-whitening launch of asmc_pcn_ysplit_end (asmc_pcn_drive.hip) with the
 //     slot as its output, so that a recorded row is what ending the session at that step returns.
 // The copy is memory bound (n d s bytes in, n d s out): one 16-byte vector per lane and consecutive lanes on consecutive
 // vectors where the row length, the pitch and both pointers are multiples of 16 bytes; element-wise, equally coalesced,

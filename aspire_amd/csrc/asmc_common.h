@@ -190,7 +190,7 @@ int asmc_chain_rows_launch(asmc_ctx* ctx, const asmc_chain_target* c, int64_t sl
 // ... the carried densities alone (the rows come from another launch)
 int asmc_chain_scalars_launch(asmc_ctx* ctx, const asmc_chain_target* c, int64_t slot, const double* ll, const double* lp,
                               hipStream_t st);
-// asmc_pcn.hip: the un-whitening launch of asmc_pcn_ysplit_end with its output pointed at x_out [n, d]; `repack`: pack the
+// asmc_pcn_drive.hip: the un-whitening launch of asmc_pcn_ysplit_end with its output pointed at x_out [n, d]; `repack`: pack the
 // parameter tables first, as asmc_pcn_ysplit_end does (the recorder packs them only when someone else has since)
 int asmc_pcn_ysplit_unwhiten(asmc_ctx* ctx, int64_t n, void* x_out, const asmc_pcn_params* prm, bool repack, hipStream_t st);
 

@@ -1,4 +1,5 @@
-// asmc_pcn.hip — pCN mutation: the step kernels, their host drivers, the zero-padding scheme.
+// asmc_pcn.hip — pCN mutation: the step kernels, their launchers (the templates, and in front of them the non-template launch
+// functions that the drivers of asmc_pcn_drive.hip call: asmc_pcn_shared.h), the mutation read-back, the zero-padding scheme.
 // (The proposal draw and the built-in densities live in asmc_density.hip, the population moments and the reference fit in
 // asmc_moments.hip; asmc_pcn_shared.h holds what they share with this file.)
 //
@@ -268,40 +269,7 @@ __device__ __forceinline__ void tri_matvec_inplace(const double* __restrict__ A,
     }
 }
 
-// MODE 0: one pCN step on x (whiten, propose, un-whiten, evaluate, accept)            — any built-in target
-// MODE 1: one pCN step on the WHITENED state y = Linv (x - mu) carried in the x buffer: y' = a y + rho xi needs
-//         no mat-vec, x' = mu + L y' is formed four rows at a time and consumed on the fly by the three
-//         (single-component) quadratic forms, so it is never materialised: one mat-vec per step instead of two
-// MODE 2: x -> y in place (start of a mutation);  MODE 3: y -> x in place + re-evaluate ll/lp/lq at the stored x
-#define PCN_X_STEP 0
-#define PCN_Y_STEP 1
-#define PCN_WHITEN 2
-#define PCN_UNWHITEN 3
-#define PCN_UNWHITEN_X 4  // y -> x in place, carried ll/lp/lq untouched (flow-proposal path)
-#define PCN_X_STEP_T 5    // PCN_X_STEP / PCN_Y_STEP with the Student-t reference (tpCN), selected at compile time
-#define PCN_Y_STEP_T 6
-// whitened state kept COORDINATE-MAJOR in a scratch buffer (ys[j * n_pad + i]) for the length of a mutation: the step
-// kernel then needs no LDS staging at all (lane i reads 8 B of 64 consecutive particles per coordinate: 512-B coalesced
-// loads straight into registers), so its occupancy is set by registers (3 waves/SIMD) instead of the 17 KB LDS tile
-// (2 waves/SIMD), and rejected proposals cost no store.  x itself is only read by the first and written by the last.
-#define PCN_WHITEN_S 7      // x (row-major) -> ys
-#define PCN_Y_STEP_S 8      // step on ys
-#define PCN_Y_STEP_TS 9     // ... Student-t reference
-#define PCN_UNWHITEN_S 10   // ys -> x (row-major), ll / lp / lq re-evaluated at the stored x
-#define PCN_UNWHITEN_XS 11  // ys -> x (row-major), carried ll / lp / lq untouched (flow-proposal path)
-// proposal half of the split path (arbitrary Python callables evaluate the densities between propose and accept):
-// x' -> the row-major buffer in p.ys, twice the reference's correction at y and y' -> the ll / lp arguments
-#define PCN_X_PROPOSE 12
-#define PCN_X_PROPOSE_T 13
-// the same for 16 < d < 32 on the D = 32 kernel: rows of d elements, coordinates d..31 held at zero, tables padded with
-// the identity (the generic LDS kernel needs 0.5-1.1 ms per proposal there, this one 0.3 ms)
-#define PCN_X_PROPOSE_PAD 14
-#define PCN_X_PROPOSE_PAD_T 15
-// coordinate-major whitened-state step for densities with several mixture components: x' = mu + L y' is materialised in
-// a second register array and handed to the general mixture evaluation (PCN_Y_STEP_S folds it into three quadratic
-// forms on the fly, which only works for single Gaussians); still one mat-vec per step and no LDS
-#define PCN_Y_STEP_SG 16
-#define PCN_Y_STEP_TSG 17
+// (the modes of k_pcn_reg - PCN_X_STEP .. PCN_Y_STEP_TSG - are listed and described in asmc_pcn_shared.h: the drivers name them)
 
 // 64-row tile copies for rows of `dr` < D elements (PCN_X_PROPOSE_PAD): fully unrolled, element-wise coalesced
 // accesses, row index by multiplication with magic = floor(2^32 / dr) + 1 (exact for e < 2^16) - no run-time loop, no
@@ -655,25 +623,8 @@ __global__ __launch_bounds__(ASMC_BLOCK, 2) void k_pcn_reg(int64_t n, T* __restr
 // with the blocked table: the pCN step at 168 registers spills 52 B and takes 165 us against 148 at two waves; the Student-t step
 // fits three waves by itself - profiles/r06_ab_pcn_blocked_L.txt)
 
-// Flow-proposal pCN on the whitened state, split around the flow's log-density kernel (asmc_flow.hip):
-//   PCN_FLOW_PROPOSE  y' = a y + rho xi;  x' = mu + L y'  -> x_prop tile, ll'(x'), lp'(x') (built-in targets)
-//   PCN_FLOW_ACCEPT   regenerates y' from the same Philox counters (no y' round trip through HBM), reads
-//                     ll', lp', lq' and accepts: y <- y' (accepted rows only), carried log-probs updated
-#define PCN_FLOW_PROPOSE 0
-#define PCN_FLOW_ACCEPT 1
-#define PCN_FLOW_PROPOSE_S 2  // the same with y coordinate-major in p.ys (see PCN_*_S above): propose stages only x'
-#define PCN_FLOW_ACCEPT_S 3   // through LDS, accept touches no LDS at all
-#define PCN_FLOW_PROPOSE_SX 4 // PCN_FLOW_PROPOSE_S without the built-in densities: the proposal half of the whitened-state
-                              // split session, whose densities come from the caller (arbitrary Python callables)
-#define PCN_FLOW_ACCEPT_SJ 5  // PCN_FLOW_ACCEPT_S with a carried log-Jacobian (chain in a preconditioned space): the two
-                              // arrays arrive through the y / x_prop parameters, which coordinate-major accept does not use
-// PCN_FLOW_PROPOSE_SX whose proposal lives in a preconditioned space z = T(x) (reference
-// transforms.py:294-316 inside smc/minipcn.py:105-119): the inverse transform x' = T^-1(z') and its log-Jacobian are
-// applied to the register-resident proposal, and - when the proposal flow's data transform shares T's bounded stage -
-// log q(x') is evaluated from z' in the same pass (asmc_mixture_logpdf_premap's arithmetic).  x' goes to x_prop, log|J| to
-// ll_new, log q to lp_new; lq_new carries the packed table (TRTAB_* below).  One variant per bounded stage.
-#define PCN_FLOW_PROPOSE_SXT_LOGIT 6
-#define PCN_FLOW_PROPOSE_SXT_PROBIT 7
+// Flow-proposal pCN on the whitened state, split around the flow's log-density kernel (asmc_flow.hip): the modes of
+// k_pcn_reg_flow - PCN_FLOW_PROPOSE .. PCN_FLOW_PROPOSE_SXT_PROBIT - are listed and described in asmc_pcn_shared.h.
 // packed table of the transform epilogue: TRTAB_ROWS rows of D doubles, then TRTAB_SCALARS scalars
 //   rows: kind, lower, upper, mean, std, 1/(upper-lower), 1/std, premap a, b, lo, hi, h, q mean, q precision
 //   scalars: eps, unit_logj, affine_logj, has_affine, q log-weight, has_q, minus_logj
@@ -890,7 +841,7 @@ __global__ __launch_bounds__(ASMC_BLOCK) void k_gamma_draw(int64_t n, double sha
 // before a step kernel: points pd.gam at the step's scale variates in ctx->d_gamma (tpCN only), drawing the next
 // ASMC_GAMMA_BATCH steps' worth when the step is not among those already there (one launch per eight steps instead of one
 // per step: 15 us of every 150 us step)
-static int pcn_prepare_gamma(asmc_ctx* ctx, int64_t n, PcnDev& pd, uint32_t step, hipStream_t st) {
+int pcn_prepare_gamma(asmc_ctx* ctx, int64_t n, PcnDev& pd, uint32_t step, hipStream_t st) {
     if (!(pd.nu > 0.0)) {
         pd.gam = nullptr;
         return ASMC_OK;
@@ -988,8 +939,8 @@ __global__ __launch_bounds__(1024) void k_count_sum(int nblocks, const long long
 
 // closes step t: accept count (summed across ranks through the exchange hook when one is installed), history, adaptation.
 // `last`: t is the final step of the call (a lagged adaptation closes its open block there).
-static int pcn_close_step(asmc_ctx* ctx, hipStream_t st, int grid, const long long* d_block, int64_t n, int t,
-                          long long* d_counts, double* d_rho, double* d_rho_hist, double target, int adapt, int last = 1) {
+int pcn_close_step(asmc_ctx* ctx, hipStream_t st, int grid, const long long* d_block, int64_t n, int t, long long* d_counts,
+                   double* d_rho, double* d_rho_hist, double target, int adapt, int last) {
     if (ctx->count_hook) {
         const int lag = adapt >= 2 ? adapt : 1;
         if (lag > ctx->count_cells) {
@@ -1083,8 +1034,8 @@ __global__ __launch_bounds__(ASMC_BLOCK) void k_copy_flagged_rows16(unsigned tot
     }
 }
 
-static int launch_copy_flagged(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x, const void* x_prop,
-                               const unsigned char* flags, hipStream_t st) {
+int launch_copy_flagged(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x, const void* x_prop, const unsigned char* flags,
+                        hipStream_t st) {
     const int64_t rowb = (int64_t)d * (x_dtype == ASMC_F64 ? 8 : 4);
     const int64_t cpr = rowb / 16;
     // power-of-two piece counts shift; otherwise e * (floor(2^32 / cpr) + 1) >> 32 == e / cpr, exact while e * cpr < 2^32
@@ -1153,35 +1104,16 @@ __global__ __launch_bounds__(256) void k_pcn_pack(PcnDev pd, double* __restrict_
     }
 }
 
-static int pack_pcn_tables(asmc_ctx* ctx, const PcnDev& pd, hipStream_t st, double* rho_cell = nullptr, double rho = 0.0) {
+int pack_pcn_tables(asmc_ctx* ctx, const PcnDev& pd, hipStream_t st, double* rho_cell, double rho) {
     ctx->ptab_tag = 0;
     ASMC_LAUNCH(ctx, st, "k_pcn_pack", k_pcn_pack, dim3(1), dim3(256), 0, st, pd, ctx->d_ptab, rho_cell, rho);
     ASMC_LAUNCH_CHECK();
     return ASMC_OK;
 }
 
-static bool pcn_reg_supported(int d, size_t elem, const void* x) {
+bool pcn_reg_supported(int d, size_t elem, const void* x) {
     return (d == 4 || d == 8 || d == 16 || d == 32) && (d * elem) % 16 == 0 && ((uintptr_t)x % 16) == 0 &&
            !pcn_env_generic();
-}
-
-// A call's parameters as the kernels take them: the reference, the tempering and the noise keys.  The densities and the noise
-// mode are the caller's to add - a flow mutation carries a placeholder for log q, a split session no density at all, and each
-// entry point checks the noise mode under its own name.  Everything else starts at zero (mode: PCN_X_STEP).
-static PcnDev pcn_dev_from_params(const asmc_ctx* ctx, const asmc_pcn_params* prm, int d_noise) {
-    PcnDev pd;
-    memset(&pd, 0, sizeof(pd));
-    pd.bmtab = ctx->d_bmtab;
-    pd.d = prm->d;
-    pd.d_noise = d_noise;
-    pd.beta = prm->beta;
-    pd.mu = prm->mu_dev;
-    pd.L = prm->L_dev;
-    pd.Linv = prm->Linv_dev;
-    pd.seed = prm->seed;
-    pd.gid0 = prm->gid0;
-    pd.nu = prm->nu;
-    return pd;
 }
 
 // the by-value part of a launch's parameters (the tables travel in ctx->d_ptab)
@@ -1307,7 +1239,7 @@ static int dispatch_pcn_reg_flow(asmc_ctx* ctx, int64_t n, T* y, T* x_prop, doub
 // (d > 128) are checked against the budget by the entry points, before anything is launched.
 static size_t pcn_generic_wave_bytes(int d, size_t elem) { return (size_t)64 * lds_row_stride(d * (int)elem) + (size_t)64 * 8 * d; }
 static bool pcn_generic_fits(int d, size_t elem) { return pcn_generic_wave_bytes(d, elem) <= 160 * 1024 - 1024 - BM_TAB_N * 16; }
-static int pcn_generic_check(int d, int x_dtype) {
+int pcn_generic_check(int d, int x_dtype) {
     const size_t elem = x_dtype == ASMC_F64 ? 8 : 4;
     if (d > 128 && !pcn_generic_fits(d, elem)) {
         asmc_set_error("pcn: d=%d needs %zu B of LDS per wave (unsupported)", d, pcn_generic_wave_bytes(d, elem));
@@ -1488,17 +1420,9 @@ int launch_unpad_rows(asmc_ctx* ctx, int64_t n, int d, int D, int x_dtype, const
     return ASMC_OK;
 }
 
-// The padded problem in ctx->d_xpad: the tables of `src` (a d-dimensional reference and its densities) padded to D at the
-// head, the zero-padded copy of the rows x behind them.  n_mix: how many density tables the caller uses - 3 (ll, lp, lq),
-// 2 (ll, lp: the proposal density is a flow) or 0 (the proposal half of the split path, which also gets a second row buffer
-// xq for x' before the padding is stripped).
-struct PcnPadded {
-    double *mu, *L, *Linv;  // [D], [D, D], [D, D]
-    double* mix;            // 3 x (mu[C_max, D] | prec[C_max, D])
-    void *xp, *xq;
-};
-static int pcn_pad_problem(asmc_ctx* ctx, int64_t n, int d, int D, int x_dtype, const void* x, const PcnDev& src, int n_mix,
-                           hipStream_t st, PcnPadded* out) {
+// the padded problem in ctx->d_xpad (PcnPadded, asmc_pcn_shared.h)
+int pcn_pad_problem(asmc_ctx* ctx, int64_t n, int d, int D, int x_dtype, const void* x, const PcnDev& src, int n_mix, hipStream_t st,
+                    PcnPadded* out) {
     const size_t es = x_dtype == ASMC_F64 ? 8 : 4;
     const size_t tab_doubles = (size_t)D + 2 * (size_t)D * D + (n_mix ? 3 * 2 * (size_t)ASMC_MAX_COMPONENTS * D : 0);
     const size_t tab_bytes = ((tab_doubles * 8 + 255) / 256) * 256;
@@ -1518,8 +1442,8 @@ static int pcn_pad_problem(asmc_ctx* ctx, int64_t n, int d, int D, int x_dtype, 
 }
 
 // the same from a call's parameters: *p2 = *prm at dimension D, pointing at the padded tables; *xp: the padded rows
-static int pcn_pad_params(asmc_ctx* ctx, int64_t n, const void* x, const asmc_pcn_params* prm, int D, int n_mix, hipStream_t st,
-                          asmc_pcn_params* p2, void** xp) {
+int pcn_pad_params(asmc_ctx* ctx, int64_t n, const void* x, const asmc_pcn_params* prm, int D, int n_mix, hipStream_t st,
+                   asmc_pcn_params* p2, void** xp) {
     PcnDev src;
     memset(&src, 0, sizeof(src));
     src.mu = prm->mu_dev, src.L = prm->L_dev, src.Linv = prm->Linv_dev;
@@ -1542,11 +1466,9 @@ static int pcn_pad_params(asmc_ctx* ctx, int64_t n, const void* x, const asmc_pc
     return ASMC_OK;
 }
 
-extern "C" {
-
 // coordinate-major scratch for the whitened state of one mutation (grown on demand, kept for the life of the ctx);
 // false when the device has no room for it (callers then stay on the in-place row-major path)
-static bool pcn_ensure_ysoa(asmc_ctx* ctx, int64_t n, int d, int x_dtype, PcnDev& pd, hipStream_t st, bool with_scratch = false) {
+bool pcn_ensure_ysoa(asmc_ctx* ctx, int64_t n, int d, int x_dtype, PcnDev& pd, hipStream_t st, bool with_scratch) {
     if (pcn_env_aos()) return false;
     const int64_t n_pad = ((n + 63) / 64) * 64;
     const size_t one = (size_t)n_pad * d * (x_dtype == ASMC_F64 ? 8 : 4);
@@ -1570,27 +1492,10 @@ static bool pcn_ensure_ysoa(asmc_ctx* ctx, int64_t n, int d, int x_dtype, PcnDev
     return true;
 }
 
-int asmc_pcn_set_count_hook(asmc_ctx* ctx, asmc_count_hook hook, void* user, int64_t* cell_dev, int64_t n_global) {
-    ASMC_REQUIRE(ctx != nullptr, "null ctx");
-    ASMC_REQUIRE(hook == nullptr || (cell_dev != nullptr && n_global > 0), "hook needs a device cell and n_global > 0");
-    ctx->count_hook = hook;
-    ctx->count_hook_user = user;
-    ctx->count_cell = reinterpret_cast<long long*>(cell_dev);
-    ctx->count_n_global = n_global;
-    ctx->count_cells = 1;  // (asmc_pcn_set_count_cells widens it)
-    return ASMC_OK;
-}
-
-int asmc_pcn_set_count_cells(asmc_ctx* ctx, int n_cells) {
-    ASMC_REQUIRE(ctx != nullptr && n_cells >= 1 && n_cells <= ASMC_MAX_COUNT_CELLS, "n_cells out of range");
-    ctx->count_cells = n_cells;
-    return ASMC_OK;
-}
-
 // The reference checks the carried log q for NaN after every mutation (smc/minipcn.py: "Log proposal contains NaN values").
 // The count rides on the mutation call's own read-back instead of a call and a synchronisation of its own: NaN / inf counts
 // of lq -> HP_PCN_LQ_COUNTS, read by asmc_pcn_lq_nan after the call's synchronisation.
-static int pcn_enqueue_lq_check(asmc_ctx* ctx, int64_t n, const double* lq, hipStream_t st) {
+int pcn_enqueue_lq_check(asmc_ctx* ctx, int64_t n, const double* lq, hipStream_t st) {
     const int rc = asmc_count_nonfinite_enqueue(ctx, n, lq, st);
     if (rc) return rc;
     ASMC_HIP(hipMemcpyAsync(ctx->h_pinned + HP_PCN_LQ_COUNTS, asmc_count_slot(ctx), sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, st));
@@ -1600,7 +1505,7 @@ static int pcn_enqueue_lq_check(asmc_ctx* ctx, int64_t n, const double* lq, hipS
 // A mutation call's read-back into the pinned HP_PCN_* cells (asmc_scratch.h): accept counts | step sizes | rho.
 // d_bad == NULL: counts, history and rho (-> HP_PCN_RHO) in a copy each.  Flow steps pass their non-finite-density counter: d_rho's
 // head and the history then come in ONE copy (d_rho_hist = d_rho + 8: rho lands in HP_PCN_RHO_HEAD) and *d_bad -> HP_PCN_NONFINITE.
-static int pcn_readback_enqueue(asmc_ctx* ctx, int n_steps, const void* d_bad, hipStream_t st) {
+int pcn_readback_enqueue(asmc_ctx* ctx, int n_steps, const void* d_bad, hipStream_t st) {
     double* h = ctx->h_pinned;
     ASMC_HIP(hipMemcpyAsync(h + HP_PCN_COUNTS, ctx->d_counts, sizeof(long long) * n_steps, hipMemcpyDeviceToHost, st));
     if (!d_bad) {
@@ -1614,8 +1519,8 @@ static int pcn_readback_enqueue(asmc_ctx* ctx, int n_steps, const void* d_bad, h
 }
 // ... handed out once the caller has waited for it.  flow: pcn_readback_enqueue had a d_bad; lq_checked: pcn_enqueue_lq_check
 // followed it
-static void pcn_readback_handout(asmc_ctx* ctx, int n_steps, bool flow, bool lq_checked, double* rho_out_host, int64_t* n_accept_host,
-                                 double* rho_hist_host) {
+void pcn_readback_handout(asmc_ctx* ctx, int n_steps, bool flow, bool lq_checked, double* rho_out_host, int64_t* n_accept_host,
+                          double* rho_hist_host) {
     const long long* h_counts = reinterpret_cast<const long long*>(ctx->h_pinned + HP_PCN_COUNTS);
     const double* h_rho_hist = ctx->h_pinned + HP_PCN_RHO_HIST;
     if (lq_checked) memcpy(&ctx->lq_nan, ctx->h_pinned + HP_PCN_LQ_COUNTS, sizeof(unsigned long long));
@@ -1626,451 +1531,8 @@ static void pcn_readback_handout(asmc_ctx* ctx, int n_steps, bool flow, bool lq_
     if (flow) memcpy(&ctx->flow_nonfinite, ctx->h_pinned + HP_PCN_NONFINITE, sizeof(unsigned long long));  // fused steps only (else stale zero)
 }
 
-// the exchange issued by the library: RCCL's all-reduce on the step kernels' own stream (include/asmc.h)
-typedef int (*rccl_allreduce_fn)(const void*, void*, size_t, int, int, void*, hipStream_t);
-static int rccl_count_hook(void* user, asmc_stream stream) {
-    asmc_ctx* ctx = static_cast<asmc_ctx*>(user);
-    const int nccl_int64 = 4, nccl_sum = 0;  // rccl.h: ncclInt64, ncclSum
-    return reinterpret_cast<rccl_allreduce_fn>(ctx->rccl_allreduce)(ctx->count_cell, ctx->count_cell, (size_t)ctx->count_cells, nccl_int64, nccl_sum,
-                                                                    ctx->rccl_comm, reinterpret_cast<hipStream_t>(stream));
-}
-
-int asmc_set_rccl(asmc_ctx* ctx, void* allreduce_fn, void* nccl_comm) {
-    ASMC_REQUIRE(ctx != nullptr, "null ctx");
-    ASMC_REQUIRE((allreduce_fn == nullptr) == (nccl_comm == nullptr), "function and communicator come together");
-    ctx->rccl_allreduce = allreduce_fn;
-    ctx->rccl_comm = nccl_comm;
-    return ASMC_OK;
-}
-
-int asmc_set_rccl_allgather(asmc_ctx* ctx, void* allgather_fn) {
-    ASMC_REQUIRE(ctx != nullptr, "null ctx");
-    ctx->rccl_allgather = allgather_fn;
-    return ASMC_OK;
-}
-
-// equal-sized all-gather of 8-byte elements on the library's communicator and stream (the small exchanges of owner-layout
-// resampling: evidence partials, chain states, kept counts)
-int asmc_rccl_all_gather(asmc_ctx* ctx, const void* send_dev, void* recv_dev, int64_t count, int is_int64, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && send_dev && recv_dev && count > 0, "bad arguments");
-    ASMC_REQUIRE(ctx->rccl_allgather && ctx->rccl_comm, "asmc_set_rccl / asmc_set_rccl_allgather first");
-    typedef int (*allgather_fn)(const void*, void*, size_t, int, void*, hipStream_t);
-    const int dt = is_int64 ? 4 : 8;  // rccl.h: ncclInt64, ncclFloat64
-    if (reinterpret_cast<allgather_fn>(ctx->rccl_allgather)(send_dev, recv_dev, (size_t)count, dt, ctx->rccl_comm,
-                                                            reinterpret_cast<hipStream_t>(stream)) != 0) {
-        asmc_set_error("asmc_rccl_all_gather: ncclAllGather failed");
-        return ASMC_ERR_ARG;
-    }
-    return ASMC_OK;
-}
-
-int asmc_pcn_set_count_rccl(asmc_ctx* ctx, int64_t* cell_dev, int64_t n_global) {
-    ASMC_REQUIRE(ctx != nullptr, "null ctx");
-    if (cell_dev == nullptr) return asmc_pcn_set_count_hook(ctx, nullptr, nullptr, nullptr, 0);
-    ASMC_REQUIRE(ctx->rccl_allreduce && ctx->rccl_comm, "asmc_set_rccl first");
-    return asmc_pcn_set_count_hook(ctx, rccl_count_hook, ctx, cell_dev, n_global);
-}
-
-}  // extern "C" (templates below)
-
-static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, double* lq, const asmc_pcn_params* prm,
-                           int n_steps, uint32_t step0, double* rho_inout_host, int64_t* n_accept_host, double* rho_hist_host,
-                           asmc_stream stream, int d_noise);
-
-static int pcn_mutate_padded(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, double* lq, const asmc_pcn_params* prm,
-                             int D, int n_steps, uint32_t step0, double* rho_inout_host, int64_t* n_accept_host,
-                             double* rho_hist_host, asmc_stream stream) {
-    hipStream_t st = as_stream(stream);
-    asmc_pcn_params p2;
-    void* xp = nullptr;
-    int rc = pcn_pad_params(ctx, n, x, prm, D, 3, st, &p2, &xp);
-    if (rc) return rc;
-    rc = pcn_mutate_impl(ctx, n, xp, ll, lp, lq, &p2, n_steps, step0, rho_inout_host, n_accept_host, rho_hist_host, stream, prm->d);
-    if (rc) return rc;
-    return launch_unpad_rows(ctx, n, prm->d, D, prm->x_dtype, xp, x, st);
-}
-
-extern "C" {
-
-int asmc_pcn_mutate(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, double* lq,
-                    const asmc_pcn_params* prm, int n_steps, uint32_t step0, double* rho_inout_host,
-                    int64_t* n_accept_host, double* rho_hist_host, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && prm, "null pointer");
-    ASMC_REQUIRE(prm->d > 0 && prm->d <= ASMC_MAX_DIMS, "bad d");
-    const int D = pcn_pad_dim(prm->d);
-    const bool fast_as_is = prm->d == D;
-    if (!fast_as_is && D > 0 && D <= ctx->d_max_pad && !pcn_env_generic() && !pcn_env_nopad()) {
-        ASMC_REQUIRE(ll && lp && lq && rho_inout_host && n_accept_host, "null pointer");
-        ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
-        ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
-        ASMC_REQUIRE(prm->mu_dev && prm->L_dev && prm->Linv_dev, "null reference-Gaussian pointer");
-        int rc = check_mixture(prm->log_likelihood);
-        if (!rc) rc = check_mixture(prm->log_prior);
-        if (!rc) rc = check_mixture(prm->log_q);
-        if (rc) return rc;
-        return pcn_mutate_padded(ctx, n, x, ll, lp, lq, prm, D, n_steps, step0, rho_inout_host, n_accept_host, rho_hist_host, stream);
-    }
-    return pcn_mutate_impl(ctx, n, x, ll, lp, lq, prm, n_steps, step0, rho_inout_host, n_accept_host, rho_hist_host, stream, 0);
-}
-
-static int pcn_mutate_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, double* lq, const asmc_pcn_params* prm,
-                           int n_steps, uint32_t step0, double* rho_inout_host, int64_t* n_accept_host, double* rho_hist_host,
-                           asmc_stream stream, int d_noise) {
-    ASMC_REQUIRE(ctx && x && ll && lp && lq && prm && rho_inout_host && n_accept_host, "null pointer");
-    ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
-    ASMC_REQUIRE(n_steps >= 1 && n_steps <= ASMC_MAX_PCN_STEPS, "n_steps out of range (<= 2048 per call)");
-    ASMC_REQUIRE(prm->d > 0 && prm->d <= ASMC_MAX_DIMS, "bad d");
-    ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
-    ASMC_REQUIRE(prm->mu_dev && prm->L_dev && prm->Linv_dev, "null reference-Gaussian pointer");
-    ASMC_REQUIRE(*rho_inout_host > 0.0 && *rho_inout_host <= 1.0, "rho must be in (0, 1]");
-    ASMC_REQUIRE(!(prm->nu > 0.0) || prm->nu >= 1.0, "nu must be >= 1 (or <= 0 for the Gaussian reference)");
-    int rc = check_mixture(prm->log_likelihood);
-    if (!rc) rc = check_mixture(prm->log_prior);
-    if (!rc) rc = check_mixture(prm->log_q);
-    if (!rc) rc = pcn_generic_check(prm->d, prm->x_dtype);  // (before the Gamma draw of a tpCN step)
-    if (rc) return rc;
-    const asmc_chain_target& ch = ctx->chain;
-    const bool padded = d_noise != 0;  // (then prm->d is the padded width and x the padded copy)
-    const size_t row_bytes = (size_t)prm->d * (prm->x_dtype == ASMC_F64 ? 8 : 4);
-    if (ctx->chain_on) {  // asmc_chain_set: every recorded slot of this call inside the chain
-        ASMC_REQUIRE(ch.n == n && ch.d == (padded ? d_noise : prm->d) && ch.x_dtype == prm->x_dtype, "chain target: n, d or dtype differ from the call's");
-        ASMC_REQUIRE(ch.slot0 >= 0 && ch.slot0 + n_steps / ch.stride <= ch.n_slots, "chain target: the call's steps do not fit the chain");
-        ASMC_REQUIRE(!padded || ctx->chain_rows_bytes >= (size_t)n * row_bytes, "chain target: no scratch for the padded rows");
-    }
-    hipStream_t st = as_stream(stream);
-    PcnDev pd = pcn_dev_from_params(ctx, prm, d_noise);
-    pd.ll = to_dev(prm->log_likelihood);
-    pd.lp = to_dev(prm->log_prior);
-    pd.lq = to_dev(prm->log_q);
-    pd.noise = prm->noise;
-    pd.mode = PCN_X_STEP;
-    ASMC_REQUIRE(pd.noise == ASMC_NOISE_F64 || pd.noise == ASMC_NOISE_F32, "bad noise mode");
-    // device step-size cell + history
-    double* d_rho = ctx->d_rho;            // [0]: current rho
-    double* d_rho_hist = ctx->d_rho + 8;   // [n_steps]
-    long long* d_counts = ctx->d_counts;   // [n_steps]
-    long long* d_block = ctx->d_counts + ASMC_MAX_PCN_STEPS;
-    const bool dbg = getenv("ASMC_DEBUG_TIMING") != nullptr;
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_a = now();
-    ASMC_HIP(hipStreamSynchronize(st));
-    const double t_b = now();
-    ctx->h_pinned[HP_FRONT] = *rho_inout_host;
-    ASMC_HIP(hipMemcpyAsync(d_rho, ctx->h_pinned, sizeof(double), hipMemcpyHostToDevice, st));
-    // Slot of step t of this call (asmc_chain_set).  Not whitened: the rows are x itself (un-padded on their way when the call
-    // runs on a zero-padded copy).  Whitened: the call's own un-whitening launch `unwhiten(rec)` with the slot's rows (the padded
-    // scratch, un-padded behind it) and density rows as its outputs rec[0 .. 3]; a launch that un-whitens x where it lies
-    // (`in_place`: the matrix-core and the row-major register kernels) gets a copy of the state there first.  The state itself is
-    // only read.  These are the launches that end a call of t + 1 steps: the same bits.
-    auto record_state = [&](int t, bool whitened, bool in_place, auto&& unwhiten) -> int {
-        const int64_t slot = ch.slot0 + t / ch.stride;
-        char* slot_x = static_cast<char*>(ch.x_dev) + (size_t)slot * (size_t)n * (size_t)ch.pitch * (row_bytes / prm->d);
-        if (!whitened) {
-            if (!padded) return asmc_chain_rows_launch(ctx, &ch, slot, x, ll, lp, st);
-            const int r = launch_unpad_rows(ctx, n, d_noise, prm->d, prm->x_dtype, x, slot_x, st);
-            return r ? r : asmc_chain_scalars_launch(ctx, &ch, slot, ll, lp, st);
-        }
-        void* dst = padded ? ctx->d_chain_rows : slot_x;
-        if (in_place) ASMC_HIP(hipMemcpyAsync(dst, x, (size_t)n * row_bytes, hipMemcpyDeviceToDevice, st));
-        void* rec[4] = {dst, ch.ll_dev + (size_t)slot * (size_t)n, ch.lp_dev + (size_t)slot * (size_t)n, ctx->d_chain_lq};
-        const int r = unwhiten(rec);
-        if (r || !padded) return r;
-        return launch_unpad_rows(ctx, n, d_noise, prm->d, prm->x_dtype, dst, slot_x, st);
-    };
-    if (asmc_pcn_mm_supported(pd.d, x) && !pcn_env_generic()) {
-        // d = 64 / 128: triangular mat-vecs on the fp64 matrix cores, always on the whitened state
-        rc = asmc_pcn_mm_pack(ctx, pd, st);
-        if (rc) return rc;
-        int grid = 0;
-        rc = asmc_pcn_mm_launch(ctx, n, prm->x_dtype, x, ll, lp, lq, pd, MM_WHITEN, d_rho, 0, d_block, &grid, st);
-        if (rc) return rc;
-        for (int t = 0; t < n_steps; t++) {
-            rc = pcn_prepare_gamma(ctx, n, pd, step0 + (uint32_t)t, st);
-            if (rc) return rc;
-            rc = asmc_pcn_mm_launch(ctx, n, prm->x_dtype, x, ll, lp, lq, pd, pd.nu > 0.0 ? MM_STEP_T : MM_STEP, d_rho,
-                                    step0 + (uint32_t)t, d_block, &grid, st);
-            if (rc) return rc;
-            rc = pcn_close_step(ctx, st, grid, d_block, n, t, d_counts, d_rho, d_rho_hist, prm->target_accept, prm->adapt, t == n_steps - 1);
-            if (rc) return rc;
-            if (ctx->chain_on && t % ch.stride == ch.stride - 1) {
-                rc = record_state(t, true, true, [&](void* const* rec) -> int {
-                    int g2 = 0;
-                    return asmc_pcn_mm_launch(ctx, n, prm->x_dtype, rec[0], (double*)rec[1], (double*)rec[2], (double*)rec[3], pd, MM_UNWHITEN,
-                                              d_rho, 0, d_block, &g2, st);
-                });
-                if (rc) return rc;
-            }
-        }
-        rc = asmc_pcn_mm_launch(ctx, n, prm->x_dtype, x, ll, lp, lq, pd, MM_UNWHITEN, d_rho, 0, d_block, &grid, st);
-        if (rc) return rc;
-        rc = pcn_readback_enqueue(ctx, n_steps, nullptr, st);
-        if (rc) return rc;
-        rc = pcn_enqueue_lq_check(ctx, n, lq, st);
-        if (rc) return rc;
-        ASMC_HIP(hipStreamSynchronize(st));
-        pcn_readback_handout(ctx, n_steps, false, true, rho_inout_host, n_accept_host, rho_hist_host);
-        return ASMC_OK;
-    }
-    const bool reg_ok = pcn_reg_supported(pd.d, prm->x_dtype == ASMC_F64 ? 8 : 4, x);
-    // whitened-state stepping: plain (single-component) targets, enough steps to amortise the two conversions
-    const bool single = pd.ll.C == 1 && pd.lp.C == 1 && pd.lq.C == 1;
-    bool y_state = reg_ok && n_steps >= 4 && !pcn_env_xstate();  // several components: only coordinate-major (below)
-    // whitened state in a coordinate-major scratch buffer (grown on demand, kept for the life of the ctx)
-    const bool soa = y_state && pcn_ensure_ysoa(ctx, n, pd.d, prm->x_dtype, pd, st);
-    if (!single && !soa) y_state = false;  // the row-major whitened-state kernel folds single Gaussians only
-    // `rec`: the launch works on rec[0] (rows) and rec[1 .. 3] (ll, lp, lq) instead of the population's arrays - the chain
-    // recorder's use of the un-whitening epilogue (record_state)
-    auto launch_mode = [&](int mode, uint32_t stp, int* grid, void* const* rec = nullptr) -> int {
-        if (soa) mode = mode == PCN_WHITEN ? PCN_WHITEN_S : mode == PCN_UNWHITEN ? PCN_UNWHITEN_S
-                        : mode == PCN_Y_STEP ? (single ? PCN_Y_STEP_S : PCN_Y_STEP_SG)
-                        : mode == PCN_Y_STEP_T ? (single ? PCN_Y_STEP_TS : PCN_Y_STEP_TSG) : mode;
-        pd.mode = mode;
-        const int nz = pd.noise;
-        if (mode == PCN_WHITEN || mode == PCN_UNWHITEN || mode == PCN_UNWHITEN_X || mode == PCN_WHITEN_S || mode == PCN_UNWHITEN_S)
-            pd.noise = ASMC_NOISE_F64;
-        void* xo = rec ? rec[0] : x;
-        double* llo = rec ? (double*)rec[1] : ll;
-        double* lpo = rec ? (double*)rec[2] : lp;
-        double* lqo = rec ? (double*)rec[3] : lq;
-        int r;
-        if (prm->x_dtype == ASMC_F64)
-            r = launch_pcn_step<double, 0>(ctx, n, (double*)xo, llo, lpo, lqo, pd, d_rho, stp, d_block, grid, nullptr, nullptr, nullptr, st);
-        else
-            r = launch_pcn_step<float, 0>(ctx, n, (float*)xo, llo, lpo, lqo, pd, d_rho, stp, d_block, grid, nullptr, nullptr, nullptr, st);
-        pd.noise = nz;
-        return r;
-    };
-    if (reg_ok) {
-        rc = pack_pcn_tables(ctx, pd, st);
-        if (rc) return rc;
-    }
-    int grid = 0;
-    if (y_state) {
-        rc = launch_mode(PCN_WHITEN, 0, &grid);
-        if (rc) return rc;
-    }
-    for (int t = 0; t < n_steps; t++) {
-        const bool tp = pd.nu > 0.0 && reg_ok;  // the generic kernel branches on the variates' pointer at run time
-        rc = pcn_prepare_gamma(ctx, n, pd, step0 + (uint32_t)t, st);
-        if (rc) return rc;
-        rc = launch_mode(y_state ? (tp ? PCN_Y_STEP_T : PCN_Y_STEP) : (tp ? PCN_X_STEP_T : PCN_X_STEP), step0 + (uint32_t)t, &grid);
-        if (rc) return rc;
-        rc = pcn_close_step(ctx, st, grid, d_block, n, t, d_counts, d_rho, d_rho_hist, prm->target_accept, prm->adapt, t == n_steps - 1);
-        if (rc) return rc;
-        if (ctx->chain_on && t % ch.stride == ch.stride - 1) {
-            rc = record_state(t, y_state, y_state && !soa, [&](void* const* rec) -> int {
-                int g2 = 0;
-                return launch_mode(PCN_UNWHITEN, 0, &g2, rec);
-            });
-            if (rc) return rc;
-        }
-    }
-    if (y_state) {
-        rc = launch_mode(PCN_UNWHITEN, 0, &grid);
-        if (rc) return rc;
-    }
-    const double t_c = now();
-    // read back: counts [n_steps] | rho_hist [n_steps] | rho
-    rc = pcn_readback_enqueue(ctx, n_steps, nullptr, st);
-    if (rc) return rc;
-    rc = pcn_enqueue_lq_check(ctx, n, lq, st);
-    if (rc) return rc;
-    ASMC_HIP(hipStreamSynchronize(st));
-    if (dbg) fprintf(stderr, "[asmc_pcn_mutate] sync0 %.3f ms, enqueue %.3f ms, drain %.3f ms (n_steps=%d)\n", t_b - t_a, t_c - t_b, now() - t_c, n_steps);
-    pcn_readback_handout(ctx, n_steps, false, true, rho_inout_host, n_accept_host, rho_hist_host);
-    return ASMC_OK;
-}
-
-// proposal half of the split path for the step `step` (gamma variates drawn first when pd.nu > 0): register-resident
-// kernel for d in {4, 8, 16, 32}, the same kernel on identity-padded tables for 16 < d < 32, generic LDS kernel otherwise
-static int pcn_propose_launch(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, void* x_prop, double* qf_old,
-                              double* qf_new, PcnDev pd, const double* rho_ptr, uint32_t step, hipStream_t st) {
-    int grid = 0;
-    int rc = pcn_prepare_gamma(ctx, n, pd, step, st);
-    if (rc) return rc;
-    const bool pad = d > 16 && d < 32 && !pcn_env_generic();
-    if (pad || (pcn_reg_supported(d, x_dtype == ASMC_F64 ? 8 : 4, x) && ((uintptr_t)x_prop % 16) == 0)) {
-        // d in {4, 8, 16, 32}: the register-resident kernel's proposal half (same arithmetic as the fused step);
-        // 16 < d < 32: the same kernel compiled for 32 dimensions with identity-padded tables
-        pd.dpad = pad ? 32 : 0;
-        pd.mode = pad ? (pd.nu > 0.0 ? PCN_X_PROPOSE_PAD_T : PCN_X_PROPOSE_PAD) : (pd.nu > 0.0 ? PCN_X_PROPOSE_T : PCN_X_PROPOSE);
-        pd.noise = ASMC_NOISE_F64;
-        pd.ys = x_prop;
-        rc = pack_pcn_tables(ctx, pd, st);
-        if (rc) return rc;
-        if (x_dtype == ASMC_F64)
-            return launch_pcn_step<double, 0>(ctx, n, (double*)const_cast<void*>(x), qf_old, qf_new, nullptr, pd, rho_ptr,
-                                              step, nullptr, &grid, nullptr, nullptr, nullptr, st);
-        return launch_pcn_step<float, 0>(ctx, n, (float*)const_cast<void*>(x), qf_old, qf_new, nullptr, pd, rho_ptr, step,
-                                         nullptr, &grid, nullptr, nullptr, nullptr, st);
-    }
-    if (asmc_pcn_mm_supported(d, x) && ((uintptr_t)x_prop % 16) == 0 && ctx->d_mmtab && !pcn_env_generic()) {
-        // d = 64 / 128: both mat-vecs of the proposal on the fp64 matrix cores (the generic LDS kernel took 10 / 76 ms per
-        // step at 1M particles - the path every user with Python densities and d > 32 was on)
-        pd.noise = ASMC_NOISE_F64;
-        rc = asmc_pcn_mm_pack(ctx, pd, st);
-        if (rc) return rc;
-        return asmc_pcn_mm_launch(ctx, n, x_dtype, const_cast<void*>(x), qf_old, qf_new, reinterpret_cast<double*>(x_prop), pd,
-                                  pd.nu > 0.0 ? MM_XPROPOSE_T : MM_XPROPOSE, rho_ptr, step, nullptr, &grid, st);
-    }
-    const int D = pcn_pad_dim(d);
-    if (D != d && D > 0 && D <= ctx->d_max_pad && !(D == 32 && d > 16) && !pcn_env_generic() && !pcn_env_nopad()) {
-        // any other d <= 128 (17 .. 31 have the in-kernel padding above): zero-padded copies of the rows and of the reference's
-        // tables, the D-dimensional proposal kernel with the noise masked beyond d, x' copied back without the padding
-        PcnDev src = pd;
-        src.ll.C = src.lp.C = src.lq.C = 0;
-        PcnPadded pad;
-        rc = pcn_pad_problem(ctx, n, d, D, x_dtype, x, src, 0, st, &pad);
-        if (rc) return rc;
-        PcnDev p2 = pd;
-        p2.d = D;
-        p2.d_noise = d;
-        p2.mu = pad.mu;
-        p2.L = pad.L;
-        p2.Linv = pad.Linv;
-        rc = pcn_propose_launch(ctx, n, D, x_dtype, pad.xp, pad.xq, qf_old, qf_new, p2, rho_ptr, step, st);
-        if (rc) return rc;
-        return launch_unpad_rows(ctx, n, d, D, x_dtype, pad.xq, x_prop, st);
-    }
-    if (x_dtype == ASMC_F64)
-        return launch_pcn_step<double, 1>(ctx, n, (double*)const_cast<void*>(x), nullptr, nullptr, nullptr, pd, rho_ptr,
-                                          step, nullptr, &grid, (double*)x_prop, qf_old, qf_new, st);
-    return launch_pcn_step<float, 1>(ctx, n, (float*)const_cast<void*>(x), nullptr, nullptr, nullptr, pd, rho_ptr, step,
-                                     nullptr, &grid, (float*)x_prop, qf_old, qf_new, st);
-}
-
-int asmc_pcn_propose(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, void* x_prop, double* qf_old,
-                     double* qf_new, const double* mu, const double* L, const double* Linv, double rho, double nu,
-                     uint64_t seed, uint64_t gid0, uint32_t step, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && x_prop && qf_old && qf_new && mu && L && Linv, "null pointer");
-    ASMC_REQUIRE(!(nu > 0.0) || nu >= 1.0, "nu must be >= 1 (or <= 0 for the Gaussian reference)");
-    ASMC_REQUIRE(n > 0 && n <= ctx->n_max && d > 0 && d <= ASMC_MAX_DIMS, "bad sizes");
-    ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    ASMC_REQUIRE(rho >= 0.0 && rho <= 1.0, "rho must be in (0, 1], or 0 for the device-resident step size");
-    const int fits = pcn_generic_check(d, x_dtype);
-    if (fits) return fits;
-    hipStream_t st = as_stream(stream);
-    PcnDev pd;
-    memset(&pd, 0, sizeof(pd));
-    pd.bmtab = ctx->d_bmtab;
-    pd.d = d;
-    pd.mu = mu;
-    pd.L = L;
-    pd.Linv = Linv;
-    pd.seed = seed;
-    pd.gid0 = gid0;
-    pd.nu = nu;
-    if (rho > 0.0) {  // by kernel argument: no pinned staging, no synchronisation
-        ASMC_LAUNCH(ctx, st, "k_set_scalar", k_set_scalar, dim3(1), dim3(1), 0, st, ctx->d_rho, rho);
-        ASMC_LAUNCH_CHECK();
-    }
-    return pcn_propose_launch(ctx, n, d, x_dtype, x, x_prop, qf_old, qf_new, pd, ctx->d_rho, step, st);
-}
-
-// Split path without a host round trip per step (asmc.h): the step size lives in the ctx, asmc_pcn_accept leaves its
-// count on the device, asmc_pcn_split_adapt closes the step like the fused loops do (exchange hook included).
-int asmc_pcn_split_begin(asmc_ctx* ctx, double rho0, asmc_stream stream) {
-    ASMC_REQUIRE(ctx != nullptr, "null ctx");
-    ASMC_REQUIRE(rho0 > 0.0 && rho0 <= 1.0, "rho must be in (0, 1]");
-    hipStream_t st = as_stream(stream);
-    ASMC_LAUNCH(ctx, st, "k_set_scalar", k_set_scalar, dim3(1), dim3(1), 0, st, ctx->d_rho, rho0);
-    ASMC_LAUNCH_CHECK();
-    return ASMC_OK;
-}
-
-int asmc_pcn_split_adapt(asmc_ctx* ctx, int64_t n_global, double target_accept, int t, int adapt, asmc_stream stream) {
-    ASMC_REQUIRE(ctx != nullptr, "null ctx");
-    ASMC_REQUIRE(n_global > 0 && t >= 0 && t < ASMC_MAX_PCN_STEPS, "bad n_global / step index");
-    hipStream_t st = as_stream(stream);
-    // the accept kernel's count cell (d_keys[0]) plays the part of a one-block partial
-    return pcn_close_step(ctx, st, 1, reinterpret_cast<const long long*>(ctx->d_keys), n_global, t, ctx->d_counts, ctx->d_rho,
-                          ctx->d_rho + 8, target_accept, adapt);
-}
-
-int asmc_pcn_split_end(asmc_ctx* ctx, int n_steps, int64_t* n_accept_host, double* rho_hist_host, double* rho_host,
-                       asmc_stream stream) {
-    ASMC_REQUIRE(ctx && n_accept_host && rho_host, "null pointer");
-    ASMC_REQUIRE(n_steps >= 1 && n_steps <= ASMC_MAX_PCN_STEPS, "n_steps out of range");
-    hipStream_t st = as_stream(stream);
-    ASMC_HIP(hipStreamSynchronize(st));  // pinned staging may still be in flight
-    const int rc = pcn_readback_enqueue(ctx, n_steps, nullptr, st);
-    if (rc) return rc;
-    ASMC_HIP(hipStreamSynchronize(st));
-    pcn_readback_handout(ctx, n_steps, false, false, rho_host, n_accept_host, rho_hist_host);
-    return ASMC_OK;
-}
-
-// ---- whitened-state session of the split path (asmc.h) -----------------------------------------------------------------
-static int ysplit_pd(asmc_ctx* ctx, int64_t n, const asmc_pcn_params* prm, PcnDev& pd) {
-    ASMC_REQUIRE(ctx && prm, "null pointer");
-    ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
-    ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
-    ASMC_REQUIRE(prm->mu_dev && prm->L_dev && prm->Linv_dev, "null reference pointer");
-    ASMC_REQUIRE(!(prm->nu > 0.0) || prm->nu >= 1.0, "nu must be >= 1 (or <= 0 for the Gaussian reference)");
-    pd = pcn_dev_from_params(ctx, prm, 0);  // (no built-in densities: the caller evaluates its own between propose and accept)
-    ASMC_REQUIRE(prm->noise == ASMC_NOISE_F64 || prm->noise == ASMC_NOISE_F32, "bad noise mode");
-    pd.noise = prm->noise;  // same in every call of a session: accept regenerates what propose drew
-    return ASMC_OK;
-}
-
-int asmc_pcn_ysplit_begin(asmc_ctx* ctx, int64_t n, const void* x, const asmc_pcn_params* prm, double rho0,
-                          asmc_stream stream) {
-    PcnDev pd;
-    int rc = ysplit_pd(ctx, n, prm, pd);
-    if (rc) return rc;
-    ASMC_REQUIRE(x != nullptr, "null pointer");
-    ASMC_REQUIRE(rho0 > 0.0 && rho0 <= 1.0, "rho must be in (0, 1]");
-    hipStream_t st = as_stream(stream);
-    if (!pcn_reg_supported(pd.d, prm->x_dtype == ASMC_F64 ? 8 : 4, x) || !pcn_ensure_ysoa(ctx, n, pd.d, prm->x_dtype, pd, st)) {
-        asmc_set_error("whitened-state split session: d=%d is not a register-kernel dimension or no scratch", pd.d);
-        return ASMC_ERR_UNSUPPORTED;
-    }
-    ASMC_LAUNCH(ctx, st, "k_set_scalar", k_set_scalar, dim3(1), dim3(1), 0, st, ctx->d_rho, rho0);
-    ASMC_LAUNCH_CHECK();
-    rc = pack_pcn_tables(ctx, pd, st);
-    if (rc) return rc;
-    ctx->ptab_tag = ++ctx->ysplit_seq;
-    pd.mode = PCN_WHITEN_S;
-    pd.noise = ASMC_NOISE_F64;  // (the whitening kernels draw nothing: they are instantiated under this key only)
-    int grid = 0;
-    long long* d_block = ctx->d_counts + ASMC_MAX_PCN_STEPS;
-    if (prm->x_dtype == ASMC_F64)
-        return launch_pcn_step<double, 0>(ctx, n, (double*)const_cast<void*>(x), nullptr, nullptr, nullptr, pd, ctx->d_rho, 0, d_block,
-                                          &grid, nullptr, nullptr, nullptr, st);
-    return launch_pcn_step<float, 0>(ctx, n, (float*)const_cast<void*>(x), nullptr, nullptr, nullptr, pd, ctx->d_rho, 0, d_block, &grid,
-                                     nullptr, nullptr, nullptr, st);
-}
-
-int asmc_pcn_ysplit_propose(asmc_ctx* ctx, int64_t n, const asmc_pcn_params* prm, uint32_t step, void* x_prop,
-                            asmc_stream stream) {
-    PcnDev pd;
-    int rc = ysplit_pd(ctx, n, prm, pd);
-    if (rc) return rc;
-    ASMC_REQUIRE(x_prop != nullptr && ((uintptr_t)x_prop % 16) == 0, "x_prop must be a 16-byte aligned device buffer");
-    ASMC_REQUIRE(ctx->d_ysoa != nullptr, "no session (asmc_pcn_ysplit_begin)");
-    hipStream_t st = as_stream(stream);
-    pd.ys = ctx->d_ysoa;
-    pd.n_pad = ((n + 63) / 64) * 64;
-    if (ctx->ptab_tag == 0 || ctx->ptab_tag != ctx->ysplit_seq) {
-        // someone else packed parameter tables on this context since asmc_pcn_ysplit_begin (cheap insurance; a context
-        // carries ONE mutation at a time - step size, counts and scale variates are per context - see include/asmc.h)
-        rc = pack_pcn_tables(ctx, pd, st);
-        if (rc) return rc;
-        ctx->ptab_tag = ctx->ysplit_seq;
-    }
-    rc = pcn_prepare_gamma(ctx, n, pd, step, st);
-    if (rc) return rc;
-    int grid = 0;
-    long long* d_block = ctx->d_counts + ASMC_MAX_PCN_STEPS;
-    if (prm->x_dtype == ASMC_F64)
-        return dispatch_pcn_reg_flow<double, PCN_FLOW_PROPOSE_SX>(ctx, n, nullptr, (double*)x_prop, nullptr, nullptr, nullptr, nullptr,
-                                                                  nullptr, nullptr, pd, ctx->d_rho, step, d_block, &grid, st);
-    return dispatch_pcn_reg_flow<float, PCN_FLOW_PROPOSE_SX>(ctx, n, nullptr, (float*)x_prop, nullptr, nullptr, nullptr, nullptr,
-                                                             nullptr, nullptr, pd, ctx->d_rho, step, d_block, &grid, st);
-}
-
 // packs the transform epilogue's table (TRTAB_*) from the device-resident transform / premap / mixture tables
-__global__ void k_trtab_pack(int d, const int* __restrict__ kind, const double* __restrict__ lower, const double* __restrict__ upper,
+extern "C" __global__ void k_trtab_pack(int d, const int* __restrict__ kind, const double* __restrict__ lower, const double* __restrict__ upper,
                              const double* __restrict__ mean, const double* __restrict__ sd, const double* __restrict__ premap,
                              const double* __restrict__ q_logw, const double* __restrict__ q_mu, const double* __restrict__ q_prec,
                              double eps, double unit_logj, double affine_logj, int minus_logj, double* __restrict__ out) {
@@ -2094,541 +1556,92 @@ __global__ void k_trtab_pack(int d, const int* __restrict__ kind, const double* 
     }
 }
 
-int asmc_pcn_ysplit_propose_tr(asmc_ctx* ctx, int64_t n, const asmc_pcn_params* prm, uint32_t step, const asmc_transform* t,
-                               const double* premap_dev, const asmc_mixture* qmix, int minus_logj, void* x_prop,
-                               double* logj_out, double* lq_out, asmc_stream stream) {
-    PcnDev pd;
-    int rc = ysplit_pd(ctx, n, prm, pd);
-    if (rc) return rc;
-    ASMC_REQUIRE(t && x_prop && logj_out && ((uintptr_t)x_prop % 16) == 0, "null / misaligned pointer");
-    ASMC_REQUIRE(ctx->d_ysoa != nullptr, "no session (asmc_pcn_ysplit_begin)");
-    ASMC_REQUIRE(t->d == pd.d && t->kind_dev && t->lower_dev && t->upper_dev, "transform tables missing or of another dimension");
-    ASMC_REQUIRE((t->mean_dev == nullptr) == (t->std_dev == nullptr), "affine stage needs both mean and std");
-    ASMC_REQUIRE((premap_dev == nullptr) == (qmix == nullptr) && (premap_dev == nullptr) == (lq_out == nullptr),
-                 "premap, mixture and lq_out come together");
-    ASMC_REQUIRE(!qmix || qmix->n_components == 1, "the proposal density must be a single Gaussian");
-    const int logit = (t->hints & 7) == (ASMC_TR_NO_PERIODIC | ASMC_TR_NO_PROBIT);
-    const int probit = (t->hints & 7) == (ASMC_TR_NO_PERIODIC | ASMC_TR_NO_LOGIT);
-    if (!logit && !probit) {
-        asmc_set_error("asmc_pcn_ysplit_propose_tr: the transform must be non-periodic with ONE bounded stage (hints %d)", t->hints);
-        return ASMC_ERR_UNSUPPORTED;
+// =============================================================================================
+// the launch interface of asmc_pcn_drive.hip (asmc_pcn_shared.h): the call's x_dtype becomes the template argument here
+// =============================================================================================
+int pcn_step_launch(asmc_ctx* ctx, int64_t n, int x_dtype, void* x, double* ll, double* lp, double* lq, const PcnDev& pd,
+                    const double* rho_ptr, uint32_t step, long long* block_counts, int* grid_out, hipStream_t st) {
+    if (x_dtype == ASMC_F64)
+        return launch_pcn_step<double, 0>(ctx, n, (double*)x, ll, lp, lq, pd, rho_ptr, step, block_counts, grid_out, nullptr, nullptr, nullptr, st);
+    return launch_pcn_step<float, 0>(ctx, n, (float*)x, ll, lp, lq, pd, rho_ptr, step, block_counts, grid_out, nullptr, nullptr, nullptr, st);
+}
+
+int pcn_generic_propose_launch(asmc_ctx* ctx, int64_t n, int x_dtype, const void* x, void* x_prop, double* qf_old, double* qf_new,
+                               const PcnDev& pd, const double* rho_ptr, uint32_t step, int* grid_out, hipStream_t st) {
+    if (x_dtype == ASMC_F64)
+        return launch_pcn_step<double, 1>(ctx, n, (double*)const_cast<void*>(x), nullptr, nullptr, nullptr, pd, rho_ptr, step, nullptr,
+                                          grid_out, (double*)x_prop, qf_old, qf_new, st);
+    return launch_pcn_step<float, 1>(ctx, n, (float*)const_cast<void*>(x), nullptr, nullptr, nullptr, pd, rho_ptr, step, nullptr, grid_out,
+                                     (float*)x_prop, qf_old, qf_new, st);
+}
+
+template <typename T>
+static int pcn_reg_flow_launch_t(asmc_ctx* ctx, int64_t n, int mode, T* y, T* x_prop, double* ll, double* lp, double* lq, double* ll_new,
+                                 double* lp_new, const double* lq_new, const PcnDev& pd, const double* rho_ptr, uint32_t step,
+                                 long long* block_counts, int* grid_out, hipStream_t st) {
+    switch (mode) {
+#define PCN_FLOW_MODE(MD) \
+    case MD:              \
+        return dispatch_pcn_reg_flow<T, MD>(ctx, n, y, x_prop, ll, lp, lq, ll_new, lp_new, lq_new, pd, rho_ptr, step, block_counts, grid_out, st);
+        PCN_FLOW_MODE(PCN_FLOW_PROPOSE)
+        PCN_FLOW_MODE(PCN_FLOW_ACCEPT)
+        PCN_FLOW_MODE(PCN_FLOW_PROPOSE_S)
+        PCN_FLOW_MODE(PCN_FLOW_ACCEPT_S)
+        PCN_FLOW_MODE(PCN_FLOW_PROPOSE_SX)
+        PCN_FLOW_MODE(PCN_FLOW_ACCEPT_SJ)
+        PCN_FLOW_MODE(PCN_FLOW_PROPOSE_SXT_LOGIT)
+        PCN_FLOW_MODE(PCN_FLOW_PROPOSE_SXT_PROBIT)
+#undef PCN_FLOW_MODE
+        default: break;
     }
-    hipStream_t st = as_stream(stream);
-    pd.ys = ctx->d_ysoa;
-    pd.n_pad = ((n + 63) / 64) * 64;
-    if (ctx->ptab_tag == 0 || ctx->ptab_tag != ctx->ysplit_seq) {
-        rc = pack_pcn_tables(ctx, pd, st);
-        if (rc) return rc;
-        ctx->ptab_tag = ctx->ysplit_seq;
-    }
-    rc = pcn_prepare_gamma(ctx, n, pd, step, st);
-    if (rc) return rc;
-    double* d_tab = ctx->d_small + DS_TRTAB;  // DS_TRTAB_LEN doubles
-    ASMC_LAUNCH(ctx, st, "k_trtab_pack", k_trtab_pack, dim3(1), dim3(64), 0, st, pd.d, t->kind_dev, t->lower_dev, t->upper_dev,
+    asmc_set_error("pcn flow: no kernel for mode %d", mode);
+    return ASMC_ERR_UNSUPPORTED;
+}
+
+int pcn_reg_flow_launch(asmc_ctx* ctx, int64_t n, int x_dtype, int mode, void* y, void* x_prop, double* ll, double* lp, double* lq,
+                        double* ll_new, double* lp_new, const double* lq_new, const PcnDev& pd, const double* rho_ptr, uint32_t step,
+                        long long* block_counts, int* grid_out, hipStream_t st) {
+    if (x_dtype == ASMC_F64)
+        return pcn_reg_flow_launch_t<double>(ctx, n, mode, (double*)y, (double*)x_prop, ll, lp, lq, ll_new, lp_new, lq_new, pd, rho_ptr, step,
+                                             block_counts, grid_out, st);
+    // PCN_FLOW_ACCEPT_SJ: y / x_prop carry the fp64 log-Jacobian arrays whatever the storage type - the kernel's parameters are
+    // T* (coordinate-major accept reads no state through them) and it reads the two as doubles again
+    return pcn_reg_flow_launch_t<float>(ctx, n, mode, static_cast<float*>(y), static_cast<float*>(x_prop), ll, lp, lq, ll_new, lp_new, lq_new,
+                                        pd, rho_ptr, step, block_counts, grid_out, st);
+}
+
+int pcn_set_scalar_launch(asmc_ctx* ctx, double* cell, double v, hipStream_t st) {
+    ASMC_LAUNCH(ctx, st, "k_set_scalar", k_set_scalar, dim3(1), dim3(1), 0, st, cell, v);
+    ASMC_LAUNCH_CHECK();
+    return ASMC_OK;
+}
+
+int pcn_accept_flags_launch(asmc_ctx* ctx, int64_t n, double* ll, double* lp, double* lq, const double* ll_new, const double* lp_new,
+                            const double* lq_new, double* lj_old, const double* lj_new, const double* qf_old, const double* qf_new,
+                            double beta, uint64_t seed, uint64_t gid0, uint32_t step, hipStream_t st) {
+    ASMC_HIP(hipMemsetAsync(ctx->d_keys, 0, sizeof(unsigned long long), st));
+    const int grid = grid_for(n, ASMC_BLOCK * 2, ASMC_MAX_BLOCKS);
+    ASMC_LAUNCH(ctx, st, "k_pcn_accept_flags", k_pcn_accept_flags, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, ll, lp, lq, ll_new, lp_new, lq_new,
+                lj_old, lj_new, qf_old, qf_new, beta, (unsigned long long)seed, (unsigned long long)gid0, step, ctx->d_flags, ctx->d_keys);
+    ASMC_LAUNCH_CHECK();
+    return ASMC_OK;
+}
+
+int pcn_adapt_exchanged_launch(asmc_ctx* ctx, int t, double target, int adapt, int lag, hipStream_t st) {
+    double* d_rho_hist = ctx->d_rho + 8;
+    ASMC_LAUNCH(ctx, st, "k_pcn_adapt", k_pcn_adapt, dim3(1), dim3(1024), 0, st, 1, (const long long*)ctx->count_cell, ctx->count_n_global, t,
+                ctx->d_counts, ctx->d_rho, d_rho_hist, target, adapt, (const double*)(d_rho_hist + t), 1,
+                lag > 1 ? (const long long*)ctx->count_cell : (const long long*)nullptr);
+    ASMC_LAUNCH_CHECK();
+    return ASMC_OK;
+}
+
+int pcn_trtab_pack_launch(asmc_ctx* ctx, int d, const asmc_transform* t, const double* premap_dev, const asmc_mixture* qmix,
+                          int minus_logj, double* d_tab, hipStream_t st) {
+    ASMC_LAUNCH(ctx, st, "k_trtab_pack", k_trtab_pack, dim3(1), dim3(64), 0, st, d, t->kind_dev, t->lower_dev, t->upper_dev,
                 t->mean_dev, t->std_dev, premap_dev, qmix ? qmix->logw_dev : (const double*)nullptr,
                 qmix ? qmix->mu_dev : (const double*)nullptr, qmix ? qmix->prec_dev : (const double*)nullptr, t->eps, t->unit_logj,
                 t->affine_logj, minus_logj, d_tab);
     ASMC_LAUNCH_CHECK();
-    int grid = 0;
-    long long* d_block = ctx->d_counts + ASMC_MAX_PCN_STEPS;
-#define PROPOSE_TR(TT, MD) \
-    dispatch_pcn_reg_flow<TT, MD>(ctx, n, nullptr, (TT*)x_prop, nullptr, nullptr, nullptr, logj_out, lq_out, (const double*)d_tab, pd, \
-                                  ctx->d_rho, step, d_block, &grid, st)
-    if (prm->x_dtype == ASMC_F64) return logit ? PROPOSE_TR(double, PCN_FLOW_PROPOSE_SXT_LOGIT) : PROPOSE_TR(double, PCN_FLOW_PROPOSE_SXT_PROBIT);
-    return logit ? PROPOSE_TR(float, PCN_FLOW_PROPOSE_SXT_LOGIT) : PROPOSE_TR(float, PCN_FLOW_PROPOSE_SXT_PROBIT);
-#undef PROPOSE_TR
-}
-
-int asmc_pcn_ysplit_accept(asmc_ctx* ctx, int64_t n, const asmc_pcn_params* prm, uint32_t step, double* ll, double* lp,
-                           double* lq, const double* ll_new, const double* lp_new, const double* lq_new, double* lj,
-                           const double* lj_new, int64_t n_global, int t, asmc_stream stream) {
-    PcnDev pd;
-    int rc = ysplit_pd(ctx, n, prm, pd);
-    if (rc) return rc;
-    ASMC_REQUIRE(ll && lp && lq && ll_new && lp_new && lq_new, "null pointer");
-    ASMC_REQUIRE((lj == nullptr) == (lj_new == nullptr), "log-Jacobian arrays: both or neither");
-    ASMC_REQUIRE(ctx->d_ysoa != nullptr, "no session (asmc_pcn_ysplit_begin)");
-    ASMC_REQUIRE(n_global > 0 && t >= 0 && t < ASMC_MAX_PCN_STEPS, "bad n_global / step index");
-    hipStream_t st = as_stream(stream);
-    pd.ys = ctx->d_ysoa;
-    pd.n_pad = ((n + 63) / 64) * 64;
-    rc = pcn_prepare_gamma(ctx, n, pd, step, st);  // the variates asmc_pcn_ysplit_propose drew for this step (still there; else redrawn: counter based)
-    if (rc) return rc;
-    int grid = 0;
-    long long* d_block = ctx->d_counts + ASMC_MAX_PCN_STEPS;
-    if (lj && prm->x_dtype == ASMC_F64)
-        rc = dispatch_pcn_reg_flow<double, PCN_FLOW_ACCEPT_SJ>(ctx, n, lj, const_cast<double*>(lj_new), ll, lp, lq,
-                                                               const_cast<double*>(ll_new), const_cast<double*>(lp_new), lq_new,
-                                                               pd, ctx->d_rho, step, d_block, &grid, st);
-    else if (lj)
-        rc = dispatch_pcn_reg_flow<float, PCN_FLOW_ACCEPT_SJ>(
-            ctx, n, static_cast<float*>(static_cast<void*>(lj)), static_cast<float*>(static_cast<void*>(const_cast<double*>(lj_new))), ll,
-            lp, lq, const_cast<double*>(ll_new), const_cast<double*>(lp_new), lq_new, pd, ctx->d_rho, step, d_block, &grid, st);
-    else if (prm->x_dtype == ASMC_F64)
-        rc = dispatch_pcn_reg_flow<double, PCN_FLOW_ACCEPT_S>(ctx, n, nullptr, nullptr, ll, lp, lq, const_cast<double*>(ll_new),
-                                                              const_cast<double*>(lp_new), lq_new, pd, ctx->d_rho, step, d_block,
-                                                              &grid, st);
-    else
-        rc = dispatch_pcn_reg_flow<float, PCN_FLOW_ACCEPT_S>(ctx, n, nullptr, nullptr, ll, lp, lq, const_cast<double*>(ll_new),
-                                                             const_cast<double*>(lp_new), lq_new, pd, ctx->d_rho, step, d_block,
-                                                             &grid, st);
-    if (rc) return rc;
-    return pcn_close_step(ctx, st, grid, d_block, n_global, t, ctx->d_counts, ctx->d_rho, ctx->d_rho + 8, prm->target_accept,
-                          prm->adapt);
-}
-
-}  // extern "C"
-
-// y -> x_out [n, d] of the open session (the state is only read): asmc_pcn_ysplit_end's launch, and the chain recorder's
-int asmc_pcn_ysplit_unwhiten(asmc_ctx* ctx, int64_t n, void* x, const asmc_pcn_params* prm, bool repack, hipStream_t st) {
-    PcnDev pd;
-    int rc = ysplit_pd(ctx, n, prm, pd);
-    if (rc) return rc;
-    ASMC_REQUIRE(x != nullptr && ctx->d_ysoa != nullptr, "null pointer / no session");
-    ASMC_REQUIRE(repack || pcn_reg_supported(pd.d, prm->x_dtype == ASMC_F64 ? 8 : 4, x), "x_out: a 16-byte aligned buffer of a session's d");
-    pd.ys = ctx->d_ysoa;
-    pd.n_pad = ((n + 63) / 64) * 64;
-    pd.mode = PCN_UNWHITEN_XS;
-    pd.noise = ASMC_NOISE_F64;
-    if (repack || ctx->ptab_tag == 0 || ctx->ptab_tag != ctx->ysplit_seq) {
-        rc = pack_pcn_tables(ctx, pd, st);
-        if (rc) return rc;
-        if (!repack) ctx->ptab_tag = ctx->ysplit_seq;  // (as asmc_pcn_ysplit_propose: the session's tables are back)
-    }
-    int grid = 0;
-    long long* d_block = ctx->d_counts + ASMC_MAX_PCN_STEPS;
-    if (prm->x_dtype == ASMC_F64)
-        return launch_pcn_step<double, 0>(ctx, n, (double*)x, nullptr, nullptr, nullptr, pd, ctx->d_rho, 0, d_block, &grid, nullptr,
-                                          nullptr, nullptr, st);
-    return launch_pcn_step<float, 0>(ctx, n, (float*)x, nullptr, nullptr, nullptr, pd, ctx->d_rho, 0, d_block, &grid, nullptr, nullptr,
-                                     nullptr, st);
-}
-
-extern "C" {
-
-int asmc_pcn_ysplit_end(asmc_ctx* ctx, int64_t n, void* x, const asmc_pcn_params* prm, asmc_stream stream) {
-    return asmc_pcn_ysplit_unwhiten(ctx, n, x, prm, true, as_stream(stream));
-}
-
-int asmc_pcn_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x, const void* x_prop, double* ll, double* lp,
-                    double* lq, const double* ll_new, const double* lp_new, const double* lq_new,
-                    double* lj_old, const double* lj_new, const double* qf_old, const double* qf_new,
-                    double beta, uint64_t seed, uint64_t gid0, uint32_t step, int64_t* n_accept_host,
-                    asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && x_prop && ll && lp && lq && ll_new && lp_new && lq_new && qf_old && qf_new, "null pointer");
-    ASMC_REQUIRE(n > 0 && n <= ctx->n_max && d > 0, "bad sizes");
-    ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    hipStream_t st = as_stream(stream);
-    unsigned char* flags = ctx->d_flags;
-    ASMC_HIP(hipMemsetAsync(ctx->d_keys, 0, sizeof(unsigned long long), st));
-    const int grid = grid_for(n, ASMC_BLOCK * 2, ASMC_MAX_BLOCKS);
-    ASMC_LAUNCH(ctx, st, "k_pcn_accept_flags", k_pcn_accept_flags, dim3(grid), dim3(ASMC_BLOCK), 0, st, n, ll, lp, lq, ll_new, lp_new, lq_new,
-                       lj_old, lj_new, qf_old, qf_new, beta, (unsigned long long)seed, (unsigned long long)gid0, step,
-                       flags, ctx->d_keys);
-    ASMC_LAUNCH_CHECK();
-    {
-        const int rc2 = launch_copy_flagged(ctx, n, d, x_dtype, x, x_prop, flags, st);
-        if (rc2) return rc2;
-    }
-    if (n_accept_host) {
-        unsigned long long* h = reinterpret_cast<unsigned long long*>(ctx->h_pinned);
-        ASMC_HIP(hipMemcpyAsync(h, ctx->d_keys, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        ASMC_HIP(hipStreamSynchronize(st));
-        *n_accept_host = (int64_t)h[0];
-    }
     return ASMC_OK;
 }
-
-// pCN with a coupling-flow proposal density: per step  propose -> flow log q(x') (fp32 MFMA, asmc_flow.hip) ->
-// built-in log prior / log likelihood of x' -> accept -> device-side step-size adaptation; no host round trip
-// inside the loop.  Work buffer: x' [n, d] (storage type) | q0 | q1 | ll' | lp' | lq'  (fp64 [n] each).
-int64_t asmc_pcn_flow_work_bytes(int64_t n, int d, int x_dtype) {
-    const int64_t xb = ((n * d * (x_dtype == ASMC_F64 ? 8 : 4) + 255) / 256) * 256;
-    return xb + 5 * (((n * 8 + 255) / 256) * 256);
-}
-
-// waits for a flow-mutation call's read-back (counts | step sizes | rho | non-finite count | NaNs of log q) and hands it out
-static int mutate_flow_collect(asmc_ctx* ctx, int n_steps, double* rho_out_host, int64_t* n_accept_host, double* rho_hist_host,
-                               hipStream_t st, hipEvent_t ev = nullptr) {
-    if (ev)
-        ASMC_HIP(hipEventSynchronize(ev));
-    else
-        ASMC_HIP(hipStreamSynchronize(st));
-    pcn_readback_handout(ctx, n_steps, true, true, rho_out_host, n_accept_host, rho_hist_host);
-    return ASMC_OK;
-}
-
-}  // extern "C"
-
-// d_noise > 0: a d_noise-dimensional problem zero-padded to prm->d = 32 by asmc_pcn_mutate_flow below (the flow keeps its own
-// dims = d_noise); only the one-kernel step takes it
-static int pcn_mutate_flow_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, double* lq,
-                                const asmc_pcn_params* prm, const asmc_coupling* flow, void* work_dev, int64_t work_bytes,
-                                int n_steps, uint32_t step0, double* rho_inout_host, int64_t* n_accept_host,
-                                double* rho_hist_host, asmc_stream stream, int d_noise) {
-    ASMC_REQUIRE(ctx && x && ll && lp && lq && prm && flow && work_dev && rho_inout_host && n_accept_host, "null pointer");
-    ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
-    ASMC_REQUIRE(n_steps >= 1 && n_steps <= ASMC_MAX_PCN_STEPS, "n_steps out of range (<= 2048 per call)");
-    ASMC_REQUIRE(prm->d > 0 && prm->d <= ASMC_MAX_DIMS && (d_noise > 0 ? d_noise : prm->d) == flow->dims, "bad d");
-    ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
-    ASMC_REQUIRE(prm->mu_dev && prm->L_dev && prm->Linv_dev, "null reference-Gaussian pointer");
-    ASMC_REQUIRE(*rho_inout_host > 0.0 && *rho_inout_host <= 1.0, "rho must be in (0, 1]");
-    ASMC_REQUIRE(d_noise > 0 || work_bytes >= asmc_pcn_flow_work_bytes(n, prm->d, prm->x_dtype), "work buffer too small");
-    ASMC_REQUIRE(!(prm->nu > 0.0) || prm->nu >= 1.0, "nu must be >= 1 (or <= 0 for the Gaussian reference)");
-    int rc = check_mixture(prm->log_likelihood);
-    if (!rc) rc = check_mixture(prm->log_prior);
-    if (rc) return rc;
-    hipStream_t st = as_stream(stream);
-    const int d = prm->d;
-    const int64_t xb = ((n * d * (prm->x_dtype == ASMC_F64 ? 8 : 4) + 255) / 256) * 256;
-    const int64_t vb = ((n * 8 + 255) / 256) * 256;
-    char* w = reinterpret_cast<char*>(work_dev);
-    void* x_prop = w;
-    double* q0 = reinterpret_cast<double*>(w + xb);
-    double* q1 = reinterpret_cast<double*>(w + xb + vb);
-    double* ll_new = reinterpret_cast<double*>(w + xb + 2 * vb);
-    double* lp_new = reinterpret_cast<double*>(w + xb + 3 * vb);
-    double* lq_new = reinterpret_cast<double*>(w + xb + 4 * vb);
-    PcnDev pd = pcn_dev_from_params(ctx, prm, d_noise);
-    double* d_rho = ctx->d_rho;
-    double* d_rho_hist = ctx->d_rho + 8;
-    long long* d_counts = ctx->d_counts;
-    unsigned long long* d_cnt = ctx->d_keys;  // accept counter of the current step
-    unsigned char* flags = ctx->d_flags;
-    // the step size goes to the device as a kernel argument: no pinned staging, so no synchronisation in front of this call's
-    // launches - the host enqueues the whole mutation while the reference fit's passes are still running
-    // register-resident whitened-state path (d in {4, 8, 16, 32}): x -> y once, then per step
-    // propose / flow / accept / adapt, y -> x at the end; four launches per step, no host round trip
-    const bool reg_ok = pcn_reg_supported(d, prm->x_dtype == ASMC_F64 ? 8 : 4, x) && !pcn_env_xstate();
-    if (!reg_ok) {  // (the register path's table pack carries the step size)
-        ASMC_LAUNCH(ctx, st, "k_set_scalar", k_set_scalar, dim3(1), dim3(1), 0, st, d_rho, *rho_inout_host);
-        ASMC_LAUNCH_CHECK();
-    }
-    if (reg_ok) {
-        pd.ll = to_dev(prm->log_likelihood);
-        pd.lp = to_dev(prm->log_prior);
-        pd.lq = pd.lp;  // placeholder: the proposal density is the flow
-        pd.noise = prm->noise;
-        ASMC_REQUIRE(pd.noise == ASMC_NOISE_F64 || pd.noise == ASMC_NOISE_F32, "bad noise mode");
-        rc = pack_pcn_tables(ctx, pd, st, d_rho, *rho_inout_host);
-        if (rc) return rc;
-        long long* d_block = ctx->d_counts + ASMC_MAX_PCN_STEPS;
-        int grid = 0;
-        const bool soa = pcn_ensure_ysoa(ctx, n, d, prm->x_dtype, pd, st, asmc_pcn_flow_fused_ok(prm, flow));
-        auto convert = [&](int mode) -> int {
-            PcnDev pc = pd;
-            pc.mode = !soa ? mode : mode == PCN_WHITEN ? PCN_WHITEN_S : PCN_UNWHITEN_XS;
-            pc.noise = ASMC_NOISE_F64;
-            if (prm->x_dtype == ASMC_F64)
-                return launch_pcn_step<double, 0>(ctx, n, (double*)x, ll, lp, lq, pc, d_rho, 0, d_block, &grid, nullptr, nullptr, nullptr, st);
-            return launch_pcn_step<float, 0>(ctx, n, (float*)x, ll, lp, lq, pc, d_rho, 0, d_block, &grid, nullptr, nullptr, nullptr, st);
-        };
-        rc = convert(PCN_WHITEN);
-        if (rc) return rc;
-        // one kernel per step (propose -> flow on the MFMA -> targets -> accept) where the shape allows it
-        const bool fused = soa && asmc_pcn_flow_fused_ok(prm, flow);
-        if (d_noise > 0 && !fused) {
-            asmc_set_error("asmc_pcn_mutate_flow: the zero-padded form needs the one-kernel step");
-            return ASMC_ERR_UNSUPPORTED;
-        }
-        // counters of the fused steps: [t] tile hand-out, [ASMC_MAX_PCN_STEPS + t] blocks done
-        // (sizes in multiples of 16 bytes: a ragged memset is two fill kernels)
-        if (fused) {  // ... and every tile starts in half 0 of the state allocation (tile parities: the split path's flag bytes,
-            // free here, which sit right behind the counters: ONE fill)
-            ASMC_HIP(hipMemsetAsync(ctx->d_tilectr, 0, ASMC_TILECTR_BYTES + ((size_t)((n + 63) / 64) + 15) / 16 * 16, st));
-            pd.tile_par = ctx->d_flags;
-        }
-        int img_words = 0;  // the steps' LDS image, built once per call (0: every step stages for itself)
-        if (fused) {
-            rc = asmc_pcn_flow_fused_stage(ctx, pd, flow, &img_words, st);
-            if (rc) return rc;
-        }
-        for (int t = 0; t < (fused ? n_steps : 0); t++) {
-            const uint32_t step = step0 + (uint32_t)t;
-            rc = pcn_prepare_gamma(ctx, n, pd, step, st);
-            if (rc) return rc;
-            // single rank: the step's last block adapts the step size itself; sharded: the ranks' counts are exchanged
-            // between the steps and the next step's prologue adapts (PcnAdaptArgs)
-            PcnAdaptArgs ad = {ctx->d_tilectr + ASMC_MAX_PCN_STEPS + t,
-                               reinterpret_cast<unsigned long long*>(ctx->d_tilectr + 2 * ASMC_MAX_PCN_STEPS),
-                               ctx->count_hook ? ctx->count_cell : nullptr,
-                               ctx->count_hook && t > 0 ? ctx->count_cell : nullptr, d_counts, d_rho, d_rho_hist,
-                               prm->target_accept, ctx->count_hook ? ctx->count_n_global : n, t, prm->adapt, t == n_steps - 1};
-            const int lag = prm->adapt >= 2 ? prm->adapt : 1;
-            if (ctx->count_hook && lag > ctx->count_cells) {
-                asmc_set_error("adapt_lag %d needs %d exchange cells, the installed hook has %d (asmc_pcn_set_count_cells)", lag, lag, ctx->count_cells);
-                return ASMC_ERR_ARG;
-            }
-            rc = asmc_pcn_flow_fused_launch(ctx, n, prm->x_dtype == ASMC_F64 ? ASMC_F64 : ASMC_F32, ll, lp, lq, pd, flow, d_rho, step,
-                                            ctx->d_tilectr + t, d_block, &grid, ad, img_words, st);
-            if (rc) return rc;
-            // the kernel's last block left this rank's count in the step's cell: exchange it - lagged runs at the end of a block
-            if (ctx->count_hook && ((t + 1) % lag == 0 || t == n_steps - 1)) {
-                const int hrc = ctx->count_hook(ctx->count_hook_user, reinterpret_cast<asmc_stream>(st));
-                if (hrc != 0) {
-                    asmc_set_error("accept-count exchange hook failed (%d)", hrc);
-                    return ASMC_ERR_ARG;
-                }
-                if (t == n_steps - 1) {  // nobody's prologue follows the last step
-                    ASMC_LAUNCH(ctx, st, "k_pcn_adapt", k_pcn_adapt, dim3(1), dim3(1024), 0, st, 1,
-                                (const long long*)ctx->count_cell, ctx->count_n_global, t, d_counts, d_rho, d_rho_hist,
-                                prm->target_accept, prm->adapt, (const double*)(d_rho_hist + t), 1,
-                                lag > 1 ? (const long long*)ctx->count_cell : (const long long*)nullptr);
-                    ASMC_LAUNCH_CHECK();
-                }
-            }
-        }
-        for (int t = 0; t < (fused ? 0 : n_steps); t++) {
-            const uint32_t step = step0 + (uint32_t)t;
-            rc = pcn_prepare_gamma(ctx, n, pd, step, st);
-            if (rc) return rc;
-#define FLOW_STEP(TT, MD)                                                                                               \
-    dispatch_pcn_reg_flow<TT, MD>(ctx, n, (TT*)x, (TT*)x_prop, ll, lp, lq, ll_new, lp_new, lq_new, pd, d_rho, step, d_block, \
-                                  &grid, st)
-            if (prm->x_dtype == ASMC_F64)
-                rc = soa ? FLOW_STEP(double, PCN_FLOW_PROPOSE_S) : FLOW_STEP(double, PCN_FLOW_PROPOSE);
-            else
-                rc = soa ? FLOW_STEP(float, PCN_FLOW_PROPOSE_S) : FLOW_STEP(float, PCN_FLOW_PROPOSE);
-            if (rc) return rc;
-            rc = asmc_coupling_logprob(ctx, n, prm->x_dtype, x_prop, flow, lq_new, stream);
-            if (rc) return rc;
-            if (prm->x_dtype == ASMC_F64)
-                rc = soa ? FLOW_STEP(double, PCN_FLOW_ACCEPT_S) : FLOW_STEP(double, PCN_FLOW_ACCEPT);
-            else
-                rc = soa ? FLOW_STEP(float, PCN_FLOW_ACCEPT_S) : FLOW_STEP(float, PCN_FLOW_ACCEPT);
-#undef FLOW_STEP
-            if (rc) return rc;
-            rc = pcn_close_step(ctx, st, grid, d_block, n, t, d_counts, d_rho, d_rho_hist, prm->target_accept, prm->adapt, t == n_steps - 1);
-            if (rc) return rc;
-        }
-        rc = convert(PCN_UNWHITEN_X);
-        if (rc) return rc;
-    }
-    if (d_noise > 0 && !reg_ok) {
-        asmc_set_error("asmc_pcn_mutate_flow: the zero-padded form needs the one-kernel step");
-        return ASMC_ERR_UNSUPPORTED;
-    }
-    for (int t = 0; t < (reg_ok ? 0 : n_steps); t++) {
-        const uint32_t step = step0 + (uint32_t)t;
-        rc = pcn_propose_launch(ctx, n, d, prm->x_dtype, x, x_prop, q0, q1, pd, d_rho, step, st);
-        if (rc) return rc;
-        rc = asmc_coupling_logprob(ctx, n, prm->x_dtype, x_prop, flow, lq_new, stream);
-        if (rc) return rc;
-        rc = asmc_mixture_logpdf(ctx, n, d, prm->x_dtype, x_prop, &prm->log_prior, lp_new, stream);
-        if (rc) return rc;
-        rc = asmc_mixture_logpdf(ctx, n, d, prm->x_dtype, x_prop, &prm->log_likelihood, ll_new, stream);
-        if (rc) return rc;
-        ASMC_HIP(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), st));
-        const int g1 = grid_for(n, ASMC_BLOCK * 2, ASMC_MAX_BLOCKS);
-        ASMC_LAUNCH(ctx, st, "k_pcn_accept_flags", k_pcn_accept_flags, dim3(g1), dim3(ASMC_BLOCK), 0, st, n, ll, lp, lq,
-                    (const double*)ll_new, (const double*)lp_new, (const double*)lq_new, (double*)nullptr,
-                    (const double*)nullptr, (const double*)q0, (const double*)q1, prm->beta, (unsigned long long)prm->seed,
-                    (unsigned long long)prm->gid0, step, flags, d_cnt);
-        ASMC_LAUNCH_CHECK();
-        rc = launch_copy_flagged(ctx, n, d, prm->x_dtype, x, x_prop, flags, st);
-        if (rc) return rc;
-        rc = pcn_close_step(ctx, st, 1, (const long long*)d_cnt, n, t, d_counts, d_rho, d_rho_hist, prm->target_accept, prm->adapt, t == n_steps - 1);
-        if (rc) return rc;
-    }
-    rc = pcn_readback_enqueue(ctx, n_steps, ctx->d_tilectr + 2 * ASMC_MAX_PCN_STEPS, st);
-    if (rc) return rc;
-    rc = pcn_enqueue_lq_check(ctx, n, lq, st);
-    if (rc) return rc;
-    if (ctx->mutate_defer) {  // asmc_pcn_mutate_flow_enqueue: the results wait in pinned memory for asmc_pcn_mutate_flow_result
-        if (!ctx->ev_mutate) ASMC_HIP(hipEventCreateWithFlags(&ctx->ev_mutate, hipEventDisableTiming));
-        ASMC_HIP(hipEventRecord(ctx->ev_mutate, st));  // _result waits for THIS point, not for what the caller enqueues behind it
-        ctx->mutate_pending_steps = n_steps;
-        return ASMC_OK;
-    }
-    return mutate_flow_collect(ctx, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st);
-}
-
-// 32 < d <= 128 (x: the state with D = 64 / 128 columns - the problem itself or its zero-padded copy, d_noise = its real
-// dimension then): whiten, n_steps launches of the one-kernel step on 16-particle groups (asmc_flow16.hip), un-whiten.  The
-// carried ll / lp / lq are the step kernel's own (MM_UNWHITEN_X re-evaluates nothing).
-static int pcn_mutate_flow16_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, double* lq, const asmc_pcn_params* prm,
-                                  const asmc_coupling* flow, int n_steps, uint32_t step0, double* rho_inout_host,
-                                  int64_t* n_accept_host, double* rho_hist_host, asmc_stream stream, int d_noise) {
-    ASMC_REQUIRE(ctx && x && ll && lp && lq && prm && flow && rho_inout_host && n_accept_host, "null pointer");
-    ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
-    ASMC_REQUIRE(n_steps >= 1 && n_steps <= ASMC_MAX_PCN_STEPS, "n_steps out of range (<= 2048 per call)");
-    ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
-    ASMC_REQUIRE(prm->mu_dev && prm->L_dev && prm->Linv_dev, "null reference-Gaussian pointer");
-    ASMC_REQUIRE(*rho_inout_host > 0.0 && *rho_inout_host <= 1.0, "rho must be in (0, 1]");
-    ASMC_REQUIRE(!(prm->nu > 0.0) || prm->nu >= 1.0, "nu must be >= 1 (or <= 0 for the Gaussian reference)");
-    ASMC_REQUIRE(prm->noise == ASMC_NOISE_F64 || prm->noise == ASMC_NOISE_F32, "bad noise mode");
-    ASMC_REQUIRE(ctx->d_mmtab != nullptr && ((uintptr_t)x % 16) == 0, "flow16: ctx was created with d_max <= 32, or a misaligned state");
-    hipStream_t st = as_stream(stream);
-    PcnDev pd = pcn_dev_from_params(ctx, prm, d_noise);
-    pd.ll = to_dev(prm->log_likelihood);
-    pd.lp = to_dev(prm->log_prior);
-    pd.lq = pd.lp;  // placeholder: the proposal density is the flow
-    pd.noise = prm->noise;
-    double* d_rho = ctx->d_rho;
-    double* d_rho_hist = ctx->d_rho + 8;
-    long long* d_counts = ctx->d_counts;
-    long long* d_block = ctx->d_counts + ASMC_MAX_PCN_STEPS;
-    unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(ctx->d_tilectr + 2 * ASMC_MAX_PCN_STEPS);
-    ASMC_LAUNCH(ctx, st, "k_set_scalar", k_set_scalar, dim3(1), dim3(1), 0, st, d_rho, *rho_inout_host);
-    ASMC_LAUNCH_CHECK();
-    ASMC_HIP(hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), st));
-    int rc = asmc_pcn_mm_pack(ctx, pd, st);
-    if (rc) return rc;
-    rc = asmc_pcn_flow16_tables(ctx, pd, flow, st);
-    if (rc) return rc;
-    int grid = 0;
-    rc = asmc_pcn_mm_launch(ctx, n, prm->x_dtype, x, ll, lp, lq, pd, MM_WHITEN, d_rho, 0, d_block, &grid, st);
-    if (rc) return rc;
-    for (int t = 0; t < n_steps; t++) {
-        const uint32_t step = step0 + (uint32_t)t;
-        rc = pcn_prepare_gamma(ctx, n, pd, step, st);
-        if (rc) return rc;
-        rc = asmc_pcn_flow16_launch(ctx, n, prm->x_dtype, x, ll, lp, lq, pd, flow, d_rho, step, d_block, &grid, d_bad, st);
-        if (rc) return rc;
-        rc = pcn_close_step(ctx, st, grid, d_block, n, t, d_counts, d_rho, d_rho_hist, prm->target_accept, prm->adapt, t == n_steps - 1);
-        if (rc) return rc;
-    }
-    rc = asmc_pcn_mm_launch(ctx, n, prm->x_dtype, x, ll, lp, lq, pd, MM_UNWHITEN_X, d_rho, 0, d_block, &grid, st);
-    if (rc) return rc;
-    rc = pcn_readback_enqueue(ctx, n_steps, d_bad, st);
-    if (rc) return rc;
-    rc = pcn_enqueue_lq_check(ctx, n, lq, st);
-    if (rc) return rc;
-    if (ctx->mutate_defer) {
-        if (!ctx->ev_mutate) ASMC_HIP(hipEventCreateWithFlags(&ctx->ev_mutate, hipEventDisableTiming));
-        ASMC_HIP(hipEventRecord(ctx->ev_mutate, st));
-        ctx->mutate_pending_steps = n_steps;
-        return ASMC_OK;
-    }
-    return mutate_flow_collect(ctx, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st);
-}
-
-// The tail of a flow mutation on a zero-padded copy xp of the state x.  The un-padding copy must sit behind the mutation on the
-// stream AND in front of the read-back's synchronisation: the blocking form returns with x final (it used to synchronise
-// inside the implementation and enqueue the copy after that, so a C caller reading x on another stream saw the padded run's
-// input).  So the implementation always runs deferred here, the copy follows, and the blocking form collects afterwards.
-template <typename Impl>
-static int pcn_flow_padded_tail(asmc_ctx* ctx, int64_t n, int d, int D, int x_dtype, const void* xp, void* x, int n_steps,
-                                double* rho_inout_host, int64_t* n_accept_host, double* rho_hist_host, hipStream_t st, Impl impl) {
-    const int caller_defers = ctx->mutate_defer;
-    ctx->mutate_defer = 1;
-    int rc = impl();
-    ctx->mutate_defer = caller_defers;
-    if (rc) return rc;
-    rc = launch_unpad_rows(ctx, n, d, D, x_dtype, xp, x, st);
-    if (rc) return rc;
-    if (caller_defers) return ASMC_OK;  // asmc_pcn_mutate_flow_result waits for the mutation's event; the copy is stream-ordered behind it
-    ctx->mutate_pending_steps = 0;
-    // (stream synchronisation, not the event recorded in front of the copy: x must be final when this call returns)
-    return mutate_flow_collect(ctx, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st);
-}
-
-extern "C" {
-
-int asmc_pcn_mutate_flow(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, double* lq,
-                         const asmc_pcn_params* prm, const asmc_coupling* flow, void* work_dev, int64_t work_bytes,
-                         int n_steps, uint32_t step0, double* rho_inout_host, int64_t* n_accept_host,
-                         double* rho_hist_host, asmc_stream stream) {
-    ASMC_REQUIRE(ctx && x && prm && flow, "null pointer");
-    if (ctx->chain_on) {  // (an MCMC target has no proposal-density term: nothing to record from the flow-proposal step)
-        asmc_set_error("asmc_pcn_mutate_flow: the chain recorder is honoured by asmc_pcn_mutate only (asmc_chain_clear first)");
-        return ASMC_ERR_UNSUPPORTED;
-    }
-    ASMC_REQUIRE(flow->affine == ASMC_AFFINE_TANH || (flow->affine == ASMC_AFFINE_SOFTCLIP && flow->kind == ASMC_FLOW_MAF),
-                 "bad affine form (the soft-clipped form is for autoregressive flows)");
-    // Fewer than 32 dimensions: the one-kernel step on a zero-padded copy (pcn_mutate_padded's scheme: padded rows and tables,
-    // the identity beyond d, no noise there) wherever the flow's shape is one the kernel takes - any even d for a coupling flow,
-    // any d for an autoregressive one.  Round 3 ran propose / flow / accept kernels at d = 8 / 16 (0.35 / 0.42 ms per step
-    // at 1M particles) and the x-state split path at the other d (0.8 ms at d = 20).
-    // More than 32 dimensions (round 5): the one-kernel step on 16-particle groups at D = 64 / 128 (asmc_flow16.hip), the
-    // problem zero-padded to D when it is narrower.  Round 4 ran propose / flow / targets / accept / copy kernels at 32 < d <= 64
-    // with a coupling flow (1.2 - 1.8 ms per step at 1M particles) and had no device path for an autoregressive flow there.
-    // (... and at d <= 32 when the flow itself lives in that layout: asmc_flow_layout = 1, an autoregressive flow of hidden width 128)
-    const bool lay16 = asmc_flow_layout(flow->kind, flow->dims, flow->hidden) == 1;
-    if ((prm->d > 32 || lay16) && prm->d <= 128 && prm->d == flow->dims && ctx->d_mmtab && !pcn_env_generic() && !pcn_env_nopad() &&
-        !pcn_env_xstate()) {
-        const int d = prm->d, D = d <= 64 ? 64 : 128;
-        asmc_pcn_params p16 = *prm;
-        p16.d = D;
-        if ((D <= ctx->d_max_pad || d <= 32) && asmc_pcn_flow16_ok(&p16, flow)) {
-            ASMC_REQUIRE(ll && lp && lq && rho_inout_host && n_accept_host, "null pointer");
-            ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
-            ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
-            ASMC_REQUIRE(prm->mu_dev && prm->L_dev && prm->Linv_dev, "null reference-Gaussian pointer");
-            int rc = check_mixture(prm->log_likelihood);
-            if (!rc) rc = check_mixture(prm->log_prior);
-            if (rc) return rc;
-            hipStream_t st = as_stream(stream);
-            if (d == D && ((uintptr_t)x % 16) == 0)
-                return pcn_mutate_flow16_impl(ctx, n, x, ll, lp, lq, prm, flow, n_steps, step0, rho_inout_host, n_accept_host, rho_hist_host,
-                                              stream, 0);
-            void* xp = nullptr;
-            rc = pcn_pad_params(ctx, n, x, prm, D, 2, st, &p16, &xp);
-            if (rc) return rc;
-            return pcn_flow_padded_tail(ctx, n, d, D, prm->x_dtype, xp, x, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st, [&]() {
-                return pcn_mutate_flow16_impl(ctx, n, xp, ll, lp, lq, &p16, flow, n_steps, step0, rho_inout_host, n_accept_host,
-                                              rho_hist_host, stream, d);
-            });
-        }
-    }
-    asmc_pcn_params p2 = *prm;
-    p2.d = 32;
-    if (prm->d >= 2 && prm->d < 32 && prm->d == flow->dims && 32 <= ctx->d_max_pad && !pcn_env_generic() &&
-        !pcn_env_nopad() && asmc_pcn_flow_fused_ok(&p2, flow) && !pcn_env_aos() && !pcn_env_xstate()) {
-        ASMC_REQUIRE(ll && lp && lq && rho_inout_host && n_accept_host && work_dev, "null pointer");
-        ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
-        ASMC_REQUIRE(prm->x_dtype == ASMC_F64 || prm->x_dtype == ASMC_F32, "bad x_dtype");
-        ASMC_REQUIRE(prm->mu_dev && prm->L_dev && prm->Linv_dev, "null reference-Gaussian pointer");
-        ASMC_REQUIRE(work_bytes >= asmc_pcn_flow_work_bytes(n, prm->d, prm->x_dtype), "work buffer too small");  // (as documented, whichever path serves the call)
-        int rc = check_mixture(prm->log_likelihood);
-        if (!rc) rc = check_mixture(prm->log_prior);
-        if (rc) return rc;
-        hipStream_t st = as_stream(stream);
-        const int d = prm->d, D = 32;
-        void* xp = nullptr;
-        rc = pcn_pad_params(ctx, n, x, prm, D, 2, st, &p2, &xp);
-        if (rc) return rc;
-        rc = pcn_flow_padded_tail(ctx, n, d, D, prm->x_dtype, xp, x, n_steps, rho_inout_host, n_accept_host, rho_hist_host, st, [&]() {
-            return pcn_mutate_flow_impl(ctx, n, xp, ll, lp, lq, &p2, flow, work_dev, work_bytes, n_steps, step0, rho_inout_host,
-                                        n_accept_host, rho_hist_host, stream, d);
-        });
-        if (rc == ASMC_ERR_UNSUPPORTED) {
-            // the one-kernel step declined after the pre-check (no register path for this pointer, no coordinate-major state): nothing
-            // of the caller's has been touched yet (only the padded copy was whitened) - the unpadded path serves the shape, as before
-            // (only the implementation answers this code: the tail's own launches and copies fail with ASMC_ERR_HIP)
-            ctx->mutate_pending_steps = 0;
-            return pcn_mutate_flow_impl(ctx, n, x, ll, lp, lq, prm, flow, work_dev, work_bytes, n_steps, step0, rho_inout_host,
-                                        n_accept_host, rho_hist_host, stream, 0);
-        }
-        return rc;
-    }
-    return pcn_mutate_flow_impl(ctx, n, x, ll, lp, lq, prm, flow, work_dev, work_bytes, n_steps, step0, rho_inout_host, n_accept_host,
-                                rho_hist_host, stream, 0);
-}
-
-int asmc_pcn_mutate_flow_enqueue(asmc_ctx* ctx, int64_t n, void* x, double* ll, double* lp, double* lq,
-                                 const asmc_pcn_params* prm, const asmc_coupling* flow, void* work_dev, int64_t work_bytes,
-                                 int n_steps, uint32_t step0, double rho, asmc_stream stream) {
-    ASMC_REQUIRE(ctx != nullptr, "null ctx");
-    ASMC_REQUIRE(ctx->mutate_pending_steps == 0, "a deferred mutation is still pending (asmc_pcn_mutate_flow_result)");
-    int64_t dummy_acc = 0;
-    ctx->mutate_defer = 1;
-    const int rc = asmc_pcn_mutate_flow(ctx, n, x, ll, lp, lq, prm, flow, work_dev, work_bytes, n_steps, step0, &rho, &dummy_acc,
-                                        nullptr, stream);
-    ctx->mutate_defer = 0;
-    return rc;
-}
-
-int asmc_pcn_mutate_flow_result(asmc_ctx* ctx, int n_steps, double* rho_out_host, int64_t* n_accept_host, double* rho_hist_host,
-                                asmc_stream stream) {
-    ASMC_REQUIRE(ctx && rho_out_host && n_accept_host, "null pointer");
-    ASMC_REQUIRE(ctx->mutate_pending_steps == n_steps && n_steps > 0, "no deferred mutation of this length is pending");
-    ctx->mutate_pending_steps = 0;
-    return mutate_flow_collect(ctx, n_steps, rho_out_host, n_accept_host, rho_hist_host, as_stream(stream), ctx->ev_mutate);
-}
-
-int64_t asmc_pcn_flow_nonfinite(asmc_ctx* ctx) { return ctx ? (int64_t)ctx->flow_nonfinite : -1; }
-
-int64_t asmc_pcn_lq_nan(asmc_ctx* ctx) { return ctx ? (int64_t)ctx->lq_nan : -1; }
-
-}  // extern "C"

@@ -1028,16 +1028,30 @@ class HipEngine:
             check(self.lib.asmc_pcn_set_count_cells(self._ctx, k), "asmc_pcn_set_count_cells")
             self._count_active = k
 
+    def _pcn_params(self, x, beta, mu, L, Linv, mixes, seed, gid0, target_accept, adapt, noise, nu) -> AsmcPcnParams:
+        """asmc_pcn_params of a call on the state x.  `mixes`: the built-in densities (ll, lp, lq) - two: log q is a flow and the
+        prior stands in its place; None: the caller evaluates its own (split session)."""
+        cs = [m.c_struct() for m in mixes] if mixes is not None else [AsmcMixture(), AsmcMixture(), AsmcMixture()]
+        if len(cs) == 2:
+            cs.append(mixes[1].c_struct())
+        return AsmcPcnParams(x.shape[1], self._xdt(x), beta, mu.data_ptr(), L.data_ptr(), Linv.data_ptr(), *cs, seed, gid0,
+                             target_accept, int(adapt), {"f64": 0, "f32": 1}[noise], float(nu))
+
+    def _flow_work_for(self, x) -> int:
+        """Grows the scratch of pcn_mutate_flow to what a call on x needs; returns that size in bytes."""
+        nbytes = self.lib.asmc_pcn_flow_work_bytes(x.shape[0], x.shape[1], self._xdt(x))
+        if self._flow_work is None or self._flow_work.numel() < nbytes:
+            self._flow_work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return nbytes
+
     def pcn_mutate(self, x, ll, lp, lq, beta, mu, L, Linv, t_ll, t_lp, t_lq, seed, gid0, rho, n_steps, step0=0,
                    target_accept=0.234, adapt=True, noise="f64", nu=0.0):
         """n_steps fused pCN steps in place (nu > 0: t-preconditioned steps with a Student-t reference).
         Returns (n_accept[n_steps], rho_hist[n_steps], rho_out)."""
         self._chk3(ll, lp, lq)
         self._count_cells_for(adapt)
-        n, d = x.shape
-        prm = AsmcPcnParams(d, self._xdt(x), beta, mu.data_ptr(), L.data_ptr(), Linv.data_ptr(), t_ll.c_struct(),
-                            t_lp.c_struct(), t_lq.c_struct(), seed, gid0, target_accept, int(adapt),
-                            {"f64": 0, "f32": 1}[noise], float(nu))
+        n = x.shape[0]
+        prm = self._pcn_params(x, beta, mu, L, Linv, (t_ll, t_lp, t_lq), seed, gid0, target_accept, adapt, noise, nu)
         n_acc = np.zeros(n_steps, dtype=np.int64)
         rho_hist = np.zeros(n_steps)
         rho_io = ctypes.c_double(rho)
@@ -1052,13 +1066,9 @@ class HipEngine:
         """pcn_mutate with a coupling-flow proposal density (log_q evaluated on the MFMA each step)."""
         self._chk3(ll, lp, lq)
         self._count_cells_for(adapt)
-        n, d = x.shape
-        prm = AsmcPcnParams(d, self._xdt(x), beta, mu.data_ptr(), L.data_ptr(), Linv.data_ptr(), t_ll.c_struct(),
-                            t_lp.c_struct(), t_lp.c_struct(), seed, gid0, target_accept, int(adapt),
-                            {"f64": 0, "f32": 1}[noise], float(nu))
-        nbytes = self.lib.asmc_pcn_flow_work_bytes(n, d, self._xdt(x))
-        if self._flow_work is None or self._flow_work.numel() < nbytes:
-            self._flow_work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        n = x.shape[0]
+        prm = self._pcn_params(x, beta, mu, L, Linv, (t_ll, t_lp), seed, gid0, target_accept, adapt, noise, nu)
+        nbytes = self._flow_work_for(x)
         cs = flow.c_struct()
         n_acc = np.zeros(n_steps, dtype=np.int64)
         rho_hist = np.zeros(n_steps)
@@ -1075,13 +1085,9 @@ class HipEngine:
         synchronises and returns what `pcn_mutate_flow` returns.  The caller may enqueue more behind it in between."""
         self._chk3(ll, lp, lq)
         self._count_cells_for(adapt)
-        n, d = x.shape
-        prm = AsmcPcnParams(d, self._xdt(x), beta, mu.data_ptr(), L.data_ptr(), Linv.data_ptr(), t_ll.c_struct(),
-                            t_lp.c_struct(), t_lp.c_struct(), seed, gid0, target_accept, int(adapt),
-                            {"f64": 0, "f32": 1}[noise], float(nu))
-        nbytes = self.lib.asmc_pcn_flow_work_bytes(n, d, self._xdt(x))
-        if self._flow_work is None or self._flow_work.numel() < nbytes:
-            self._flow_work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        n = x.shape[0]
+        prm = self._pcn_params(x, beta, mu, L, Linv, (t_ll, t_lp), seed, gid0, target_accept, adapt, noise, nu)
+        nbytes = self._flow_work_for(x)
         cs = flow.c_struct()
         check(self.lib.asmc_pcn_mutate_flow_enqueue(self._ctx, n, _dptr(x), _dptr(ll), _dptr(lp), _dptr(lq), ctypes.byref(prm),
                                                     ctypes.byref(cs), _dptr(self._flow_work), nbytes, n_steps, step0,
@@ -1131,10 +1137,9 @@ class HipEngine:
                          noise="f64"):
         """Opens a session on x (left untouched until pcn_ysplit_end) and returns its handle, or None when the dimension has
         no whitened-state kernels (the caller then uses pcn_propose / pcn_accept)."""
-        n, d = x.shape
-        prm = AsmcPcnParams(d, self._xdt(x), beta, mu.data_ptr(), L.data_ptr(), Linv.data_ptr(), AsmcMixture(), AsmcMixture(),
-                            AsmcMixture(), seed, gid0, target_accept, int(adapt), {"f64": 0, "f32": 1}[noise], float(nu))
-        rc = self.lib.asmc_pcn_ysplit_begin(self._ctx, n, _dptr(x), ctypes.byref(prm), float(rho), self._stream)
+        n = x.shape[0]
+        prm = self._pcn_params(x, beta, mu, L, Linv, None, seed, gid0, target_accept, adapt, noise, nu)
+        rc = self.lib.asmc_pcn_ysplit_begin(self._ctx, n, _dptr(x),ctypes.byref(prm), float(rho), self._stream)
         if rc == _lib.ASMC_ERR_UNSUPPORTED:
             return None
         check(rc, "asmc_pcn_ysplit_begin")

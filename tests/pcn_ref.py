@@ -378,7 +378,7 @@ def problem(n, d, seed, C=1, store=np.float64):
 
 
 def case_state(d, n_steps, C, env=None):
-    """Which form of the state asmc_pcn_mutate steps on (the dispatch of pcn_mutate_impl): the matrix-core widths always whiten;
+    """Which form of the state asmc_pcn_mutate steps on (the dispatch of pcn_mutate_impl, csrc/asmc_pcn_drive.hip): the matrix-core widths always whiten;
     the register widths whiten for n_steps >= 4 - mixtures only on the coordinate-major kernels - unless ASMC_PCN_XSTATE is set;
     the generic kernel never does.  A zero-padded problem follows its padded width."""
     if env in ("ASMC_PCN_GENERIC", "big", "offset") or (env == "ASMC_PCN_NOPAD" and pad_dim(d) != d):

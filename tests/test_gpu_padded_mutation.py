@@ -1,4 +1,4 @@
-"""Flow mutations of a d without kernels of its own (csrc/asmc_pcn.hip, asmc_pcn_mutate_flow): the state is copied into
+"""Flow mutations of a d without kernels of its own (csrc/asmc_pcn_drive.hip, asmc_pcn_mutate_flow): the state is copied into
 zero-padded rows of the next supported width, the one-kernel step runs on the copy - always deferred - the rows are copied
 back, and only then does the blocking form wait for the read-back (pcn_flow_padded_tail).  A coupling flow at d = 20 runs
 padded to 32 on k_pcn_flow_fused, at d = 40 padded to 64 on k_pcn_flow16.

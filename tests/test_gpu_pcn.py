@@ -8,7 +8,8 @@ float32 terms where the storage type or the noise mode is fp32); none comes from
 |log_a - log u| the restatement itself cannot call within that tolerance is skipped from that step on; tests/test_pcn_ref.py shows on
 the CPU that every case of the table keeps those rows within pcn_ref.razor_cap.
 
-Which shape takes which path (pcn_mutate_impl, launch_pcn_step, asmc_pcn_mm_launch):
+Which shape takes which path (pcn_mutate_impl in csrc/asmc_pcn_drive.hip; launch_pcn_step behind pcn_step_launch in csrc/asmc_pcn.hip;
+asmc_pcn_mm_launch):
 
   k_pcn_reg<T, D, NOISE, MODE>   d in {4, 8, 16, 32}, 16-byte aligned x.  n_steps < 4 or ASMC_PCN_XSTATE: X_STEP / X_STEP_T;
                                  n_steps >= 4: WHITEN_S, Y_STEP_S / _TS (single Gaussians) or _SG / _TSG (mixtures), UNWHITEN_S
@@ -37,7 +38,7 @@ pytestmark = pytest.mark.gpu
 FAMILIES = ("k_pcn_reg", "k_pcn_step", "k_pcn_mm", "k_gamma_draw", "k_pcn_accept_flags", "k_copy_flagged_rows", "k_pad_rows",
             "k_unpad_rows", "k_pad_tables", "k_pcn_pack", "k_pcn_adapt", "k_count_sum")
 EXCLUDE = ("k_pcn_reg_flow",)
-# k_pcn_reg modes / k_pcn_mm modes (csrc/asmc_pcn.hip, asmc_pcn_dev.h)
+# k_pcn_reg modes / k_pcn_mm modes (csrc/asmc_pcn_shared.h, asmc_pcn_dev.h)
 X_STEP, Y_STEP, WHITEN, UNWHITEN, X_STEP_T, Y_STEP_T, WHITEN_S, Y_STEP_S, Y_STEP_TS, UNWHITEN_S = 0, 1, 2, 3, 5, 6, 7, 8, 9, 10
 X_PROPOSE, X_PROPOSE_T, X_PROPOSE_PAD, X_PROPOSE_PAD_T, Y_STEP_SG, Y_STEP_TSG, UNWHITEN_XS = 12, 13, 14, 15, 16, 17, 11
 FLOW_ACCEPT_S, FLOW_PROPOSE_SX, FLOW_ACCEPT_SJ = 3, 4, 5  # k_pcn_reg_flow modes of the split session
@@ -191,7 +192,7 @@ def gamma_launches(step0, n_steps):
 
 
 def expected_mutate(c, xd, on_big, step0=5):
-    """The instantiations one asmc_pcn_mutate call of case `c` launches: pcn_mutate_impl's dispatch, restated."""
+    """The instantiations one asmc_pcn_mutate call of case `c` launches: pcn_mutate_impl's dispatch (csrc/asmc_pcn_drive.hip), restated."""
     T, nz, tp, d, s = ("d" if c["store"] == "f64" else "f"), int(c["mode"] == "f32"), c["nu"] > 0, c["d"], c["n_steps"]
     es = 8 if T == "d" else 4
     env = c["env"]
