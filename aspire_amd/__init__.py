@@ -8,9 +8,9 @@ reference's operator interface (`samples`, `samplers`, `aspire`, `flows`, `targe
 from .aspire import Aspire
 from .flows import CouplingFlow, Flow, GaussianFlow
 from .history import SMCHistory
-from .samples import MCMCSamples, Samples, SMCSamples
+from .samples import MCMCSamples, PTMCMCSamples, Samples, SMCSamples
 from .targets import DiagGaussianMixture
 
-__all__ = ["Aspire", "Samples", "SMCSamples", "MCMCSamples", "SMCHistory", "Flow", "GaussianFlow", "CouplingFlow",
+__all__ = ["Aspire", "Samples", "SMCSamples", "MCMCSamples", "PTMCMCSamples", "SMCHistory", "Flow", "GaussianFlow", "CouplingFlow",
            "DiagGaussianMixture"]
 __version__ = "0.1.0"

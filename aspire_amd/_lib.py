@@ -26,7 +26,7 @@ COUNT_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 ASMC_BIS_REC = 40
 ASMC_SELECT_THREADS = 262144
 ASMC_STUDENT_MAX_ROWS = 16384
-ASMC_ABI_VERSION = 28
+ASMC_ABI_VERSION = 29
 ASMC_FLOW_COUPLING, ASMC_FLOW_MAF = 0, 1  # asmc_coupling.kind
 ASMC_MAX_COUNT_CELLS = 64  # asmc_pcn_set_count_cells
 ASMC_CDF_REC = 9
@@ -36,6 +36,7 @@ ASMC_NUTS_MAX_DOUBLINGS = 10
 ASMC_NUTS_VEC_Z, ASMC_NUTS_VEC_POINT, ASMC_NUTS_VEC_GRAD, ASMC_NUTS_VEC_FIXED = 6, 11, 12, 15
 ASMC_NUTS_SC_DENSITIES, ASMC_NUTS_SC_SLOTS, ASMC_NUTS_INT_SLOTS = 4, 10, 12
 ASMC_CHAIN_ROWS, ASMC_CHAIN_YS = 0, 1  # asmc_chain_record: source
+ASMC_PT_MAX_RUNGS = 64  # asmc_pt_swap / asmc_pt_evidence
 
 
 class AsmcMixture(ctypes.Structure):
@@ -290,6 +291,8 @@ SIGNATURES = {
                                _vp]),
     "asmc_chain_set": (_i, [_vp, POINTER(AsmcChainTarget)]),
     "asmc_chain_clear": (_i, [_vp]),
+    "asmc_pt_swap": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "asmc_pt_evidence": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -2,7 +2,7 @@
 
 Kept: constructor keywords (aspire.py:79-98), `fit`, `sample_posterior` (signature, kwargs routing by
 `inspect.signature`, `return_history`, `n_likelihood_evaluations`), `get_sampler_class`,
-`init_sampler`.  `sampler in {"smc", "minipcn_smc", "emcee_smc", "blackjax_smc", "minipcn", "emcee"}` is implemented natively (the hot path this
+`init_sampler`.  `sampler in {"smc", "minipcn_smc", "emcee_smc", "blackjax_smc", "minipcn", "emcee", "pt_minipcn"}` is implemented natively (the hot path this
 repository replaces); other names resolve through the `aspire.samplers` entry-point group exactly
 like the reference (aspire.py:293-304) and otherwise raise.  HDF5 checkpoint files, plotting and
 the JAX backend are out of scope.
@@ -313,6 +313,8 @@ class Aspire:
             from .samplers.mcmc import HipMiniPCN as SamplerClass
         elif sampler_type == "emcee":
             from .samplers.mcmc import HipEmcee as SamplerClass
+        elif sampler_type == "pt_minipcn":
+            from .samplers.mcmc import HipPTMiniPCN as SamplerClass
         else:
             from importlib.metadata import entry_points
 

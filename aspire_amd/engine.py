@@ -1278,6 +1278,31 @@ class HipEngine:
     def chain_clear(self):
         check(self.lib.asmc_chain_clear(self._ctx), "asmc_chain_clear")
 
+    # ---- parallel tempering of the "pt_minipcn" sampler (include/asmc.h asmc_pt_*) ---------------------------------------------------
+    def pt_swap(self, x, ll, lp, betas, seed: int, rnd: int, counts, c0=None, c1=None):
+        """Replica exchange round `rnd` on the state of len(betas) rungs (x [T W, d], rung r in rows r W .. (r + 1) W; ll, lp and
+        the optional companions c0, c1 [T W] travel with a row); `betas` [T] fp64 and `counts` [T - 1] int64 on the device, the
+        latter accumulating accepted walkers per pair.  Only enqueues."""
+        n_temps = int(betas.numel())
+        n, d = x.shape
+        assert x.is_contiguous() and n % n_temps == 0 and betas.dtype == torch.float64 and betas.is_contiguous()
+        assert counts is None or (counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= n_temps - 1)
+        for v in (ll, lp, c0, c1):
+            assert v is None or (v.dtype == torch.float64 and v.is_contiguous() and v.numel() == n)
+        check(self.lib.asmc_pt_swap(self._ctx, n_temps, n // n_temps, d, self._xdt(x), _dptr(x), _dptr(ll), _dptr(lp), _dptr(c0),
+                                    _dptr(c1), _dptr(betas), int(seed), int(rnd), _dptr(counts), self._stream), "asmc_pt_swap")
+
+    def pt_evidence(self, ll, n_temps: int, stride: int, offset: int, n: int, coef) -> np.ndarray:
+        """The evidence reductions over a recorded log-likelihood chain ll [n_temps, stride] (device, fp64), rung r's kept samples
+        being ll[r, offset : offset + n]; coef [2, n_temps]: trapezoid weights and stepping-stone scales.  Returns the
+        [n_temps + 1, 4] table of include/asmc.h asmc_pt_evidence on the host - one synchronisation."""
+        assert ll.dtype == torch.float64 and ll.is_contiguous() and ll.numel() == n_temps * stride and 0 <= offset and offset + n <= stride
+        coef_d = self.asarray(np.ascontiguousarray(coef, dtype=np.float64).reshape(2, n_temps))
+        out = self.empty((n_temps + 1, 4))
+        check(self.lib.asmc_pt_evidence(self._ctx, int(n_temps), int(stride), int(offset), int(n), _dptr(ll), _dptr(coef_d), _dptr(out),
+                                        self._stream), "asmc_pt_evidence")
+        return out.cpu().numpy()
+
     # ---- random-walk MH and HMC of the "blackjax_smc" sampler (include/asmc.h asmc_rw_* / asmc_mh_* / asmc_hmc_*) ---------------
     def rw_propose(self, x, sigma, seed: int, gid0: int, step: int, t: int):
         """y = x + sigma xi in x's dtype.  `sigma`: a float (standard deviation), a device [d] tensor (per-coordinate standard

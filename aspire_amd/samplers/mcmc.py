@@ -1,10 +1,13 @@
-"""The `"minipcn"` and `"emcee"` samplers: plain MCMC from the proposal flow's draws, every step of every walker kept on the device.
+"""The `"minipcn"`, `"emcee"` and `"pt_minipcn"` samplers: plain MCMC from the proposal flow's draws, every step of every walker kept on
+the device.
 
 `HipMiniPCN` and `HipEmcee` mirror reference src/aspire/samplers/mcmc.py:203-348 (`Emcee`, `MiniPCN`).  The transitions are this
 repository's pCN / tpCN step kernels and stretch-move kernels (csrc/asmc_pcn*.hip, csrc/asmc_stretch.hip) at beta = 1 with a zero
 log q array - the target of an MCMC run has no proposal-density term, so the flow's density is never evaluated after the initial
 draw - and the chain is written by the recorder of csrc/asmc_chain.hip.  Neither `minipcn` nor `emcee` is installed: the chains
-are this repository's specification, parity with the packages' random streams is unpinned.
+are this repository's specification, parity with the packages' random streams is unpinned.  `HipPTMiniPCN` runs
+a ladder of such chains at inverse temperatures beta_r with replica exchange between them; the reference has the
+container and the base class of a tempered sampler (samples.py:810-1205, mcmc.py:351-368) and no concrete one.
 """
 from __future__ import annotations
 
@@ -14,9 +17,9 @@ import math
 import numpy as np
 import torch
 
-from .._xp import is_torch_namespace
+from .._xp import is_torch_namespace, to_numpy
 from ..history import SMCHistory
-from ..samples import MCMCSamples, Samples
+from ..samples import MCMCSamples, PTMCMCSamples, Samples
 from ..targets import DiagGaussianMixture
 from .base import IdentityTransform, MCMCSampler, track_calls
 from .emcee_smc import MAX_CHUNK, RED_BLUE_MESSAGE, stretch_move_settings
@@ -274,3 +277,188 @@ class HipEmcee(ChainSampler):
             logger.info(f"Subsampling MCMC samples to {n_samples} samples after burn-in.")
             out = out[:n_samples]
         return out
+
+
+PT_MAX_RUNGS = 64  # include/asmc.h ASMC_PT_MAX_RUNGS
+
+
+def default_ladder(n_temps: int, beta_min: float) -> np.ndarray:
+    """beta_min^(k / (T - 2)) for k = 0 .. T - 2, then 0: geometric from 1 down to beta_min, and the prior itself, which the
+    stepping-stone estimator needs.  One rung is the posterior alone, two are posterior and prior."""
+    if n_temps < 1:
+        raise ValueError("n_temps must be at least 1")
+    if n_temps == 1:
+        return np.ones(1)
+    if not 0.0 < beta_min < 1.0:
+        raise ValueError("beta_min must lie in (0, 1)")
+    geo = np.ones(1) if n_temps == 2 else float(beta_min) ** (np.arange(n_temps - 1) / (n_temps - 2))
+    return np.concatenate((geo, [0.0]))
+
+
+class HipPTMiniPCN(ChainSampler):
+    """The `"pt_minipcn"` sampler: parallel-tempered pCN / tpCN chains with replica exchange and the evidence on the device.
+
+    Specification (this repository's own).  T rungs of W walkers; rung r targets (1 - beta_r) lq + beta_r (ll + lp)
+    with lq the prior's value, i.e. lp + beta_r ll.  The T W initial walkers come from `draw_initial_samples`, rung r takes rows
+    r W .. (r + 1) W.  Each rung has its own reference distribution, fitted to its walkers at the start (and every `refit_every`
+    steps while t < burnin), and its own step size, from min(2.38 / sqrt(d), 0.99), adapted by `pcn_adapt` with the index
+    restarting at every call of the step loop.  Rung r, walker w, step t draws the pCN streams of gid = r W + w at step t.  After
+    every `swap_every` steps one `asmc_pt_swap` with round index t / swap_every - 1 (0: never).  chain[r, t] is rung r's state
+    after the move of step t and before the exchange that may follow it.  `n_samples` only gives the default number of walkers per
+    rung - the result is the whole processed chain, which cannot be sliced -, and `n_temps` / `beta_min` are read only when `betas`
+    is not given."""
+
+    _fit_reference = HipSMC._fit_reference
+    _fit_reference_gaussian = HipSMC._fit_reference_gaussian
+    _upload_reference = HipSMC._upload_reference
+    _check_reference_fit = HipSMC._check_reference_fit
+
+    rung_acceptance = rung_step_size = swap_acceptance = evidence = None
+
+    def log_likelihood_wrapper(self, z):
+        """mcmc.py:354-360: log L at x = T^-1(z), for array input."""
+        x, _ = self.preconditioning_transform.inverse(z)
+        samples = Samples(x, xp=self.xp, dtype=self.dtype)
+        samples.log_prior = self.log_prior(samples)
+        samples.log_likelihood = self.log_likelihood(samples)
+        return to_numpy(samples.log_likelihood)
+
+    def log_prior_wrapper(self, z):
+        """mcmc.py:362-368: log pi at x = T^-1(z) plus log|det dT^-1/dz| (the Jacobian is counted here and only here)."""
+        x, logj = self.preconditioning_transform.inverse(z)
+        return self.log_prior(Samples(x, xp=self.xp, dtype=self.dtype)) + logj
+
+    @track_calls
+    def sample(self, n_samples: int | None = None, n_walkers: int | None = None, n_temps: int = 8, betas=None, beta_min: float = 1e-3,
+               n_steps: int = 100, swap_every: int = 1, burnin: int = 0, thin: int = 1, step_fn: str = "tpcn",
+               target_acceptance_rate: float = 0.234, refit_every: int | None = None, rng=None, checkpoint_callback=None,
+               checkpoint_every: int | None = None, checkpoint_file_path: str | None = None):
+        self._single_rank()
+        if step_fn not in ("pcn", "tpcn"):
+            raise NotImplementedError(f"step_fn={step_fn!r} is not implemented by the HIP step kernels; use step_fn='tpcn' or 'pcn'")
+        e = self.engine
+        rng = rng or self.rng or np.random.default_rng()
+        if not (n_walkers or n_samples):
+            raise ValueError("give n_walkers or n_samples: the number of walkers per rung defaults to n_samples")
+        if betas is None:
+            ladder = default_ladder(int(n_temps), float(beta_min))
+        else:
+            ladder = np.asarray(to_numpy(betas), dtype=np.float64)
+            if ladder.ndim != 1 or ladder.size < 1 or ladder[0] != 1.0 or np.any(np.diff(ladder) >= 0) or ladder[-1] < 0:
+                raise ValueError("betas must be a 1D array that starts at 1, decreases strictly and stays in [0, 1]")
+        n_t = int(ladder.size)
+        if n_t > PT_MAX_RUNGS:
+            raise ValueError(f"at most {PT_MAX_RUNGS} rungs, got {n_t}")
+        W, n_steps, swap_every = int(n_walkers or n_samples), int(n_steps), int(swap_every)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1")
+        if swap_every < 0 or (refit_every is not None and int(refit_every) < 1):
+            raise ValueError("swap_every must be non-negative and refit_every positive")
+        self._check_chain_memory(n_t * n_steps, W)
+        if hasattr(e, "ensure_capacity"):
+            e.ensure_capacity(n_t * W, self.dims)
+        self.history = SMCHistory()
+        self.sampler_kwargs = {"step_fn": step_fn}
+        _, z, logj, ll, lp, T = self._start(n_t * W)
+        rows = [slice(r * W, (r + 1) * W) for r in range(n_t)]
+        states = [{"rho": min(2.38 / math.sqrt(self.dims), 0.99), "step": 0, "nu": None} for _ in range(n_t)]
+        refs = [None] * n_t
+
+        def refit(r):
+            self._pcn_state = states[r]
+            mu, L, Linv, nu = self._fit_reference(z[rows[r]], W, step_fn)
+            refs[r] = (mu.clone(), L.clone(), Linv.clone(), nu)  # (the fit's outputs are views of buffers the next fit reuses)
+            self._check_reference_fit()
+
+        for r in range(n_t):
+            refit(r)
+        seed = int(rng.integers(0, 2**63 - 1, dtype=np.int64))
+        chain = e.chain_alloc(n_t * n_steps, W, self.dims, z.dtype)
+        x4, ll3, lp3 = chain.x.view(n_t, n_steps, W, self.dims), chain.ll.view(n_t, n_steps, W), chain.lp.view(n_t, n_steps, W)
+        chains = [type(chain)(x4[r], ll3[r], lp3[r]) for r in range(n_t)]
+        lq = lp.clone()  # the proposal-density slot carries the prior's value: (1 - beta) lq + beta (ll + lp) = lp + beta ll
+        betas_dev = e.asarray(ladder)
+        counts = torch.zeros(max(n_t - 1, 1), dtype=torch.int64, device=betas_dev.device)
+        builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
+        stepper = self._segment_fused if T is None and builtin else self._segment_generic
+        run = (z, logj, ll, lp, lq, T, rows, ladder, states, refs, seed, float(target_acceptance_rate), chains)
+        refit_every = None if refit_every is None else int(refit_every)
+        accepted, done, n_rounds = np.zeros(n_t), 0, 0
+        try:
+            while done < n_steps:
+                if done and refit_every and done % refit_every == 0 and done < burnin:
+                    for r in range(n_t):
+                        refit(r)
+                stops = [n_steps, done + MAX_CHUNK]
+                if swap_every:
+                    stops.append((done // swap_every + 1) * swap_every)
+                if refit_every and done < burnin:
+                    stops.append((done // refit_every + 1) * refit_every)
+                chunk = min(stops) - done
+                accepted += stepper(run, done, chunk)
+                done += chunk
+                if swap_every and n_t > 1 and done % swap_every == 0:
+                    e.pt_swap(z, ll, lp, betas_dev, seed, done // swap_every - 1, counts, c0=lq, c1=logj)
+                    n_rounds += 1
+        finally:
+            e.chain_clear()
+        self.rung_acceptance = accepted / (n_steps * W)
+        self.rung_step_size = np.array([st["rho"] for st in states])
+        tries = np.array([len(range(r % 2, n_rounds, 2)) for r in range(n_t - 1)], dtype=np.float64) * W
+        got = to_numpy(counts)[:n_t - 1].astype(np.float64)  # the one read of the device counts
+        self.swap_acceptance = np.divide(got, tries, out=np.zeros(n_t - 1), where=tries > 0)
+        self.history.mcmc_acceptance.append(float(self.rung_acceptance[0]))
+        self.history.mcmc_step_size.append(float(self.rung_step_size[0]))
+        full = PTMCMCSamples.from_chain(chain=x4, betas=ladder, log_likelihood=ll3, log_prior=lp3, parameters=self.parameters, xp=torch,
+                                        dtype=self.dtype, thin=1, burn_in=0, engine=e)
+        self.evidence = {"thermodynamic_integration": full.log_evidence_thermodynamic_integration(),
+                         "stepping_stone": full.log_evidence_stepping_stone() if ladder[-1] == 0.0 else None}
+        full = self._out(full)
+        self.checkpoint_mcmc_chain(samples=full, iteration=n_steps, checkpoint_callback=checkpoint_callback,
+                                   checkpoint_every=checkpoint_every, checkpoint_file_path=checkpoint_file_path)
+        return full.post_process(burn_in=int(burnin), thin=int(thin))
+
+    def _segment_fused(self, run, t0: int, chunk: int):
+        """Built-in mixture densities under the identity transform: per rung one asmc_pcn_mutate call on its row range with the
+        prior's mixture as the log q mixture, recorded by the chain target pointed at the rung's block.  Each call synchronises."""
+        e = self.engine
+        z, logj, ll, lp, lq, T, rows, ladder, states, refs, seed, target, chains = run
+        self.last_mutation_path = ("built-in densities: per rung the device-side step loop (asmc_pcn_mutate) at beta_r, recorded by "
+                                   "its chain target; exchange by asmc_pt_swap")
+        t_ll, t_lp = self._log_likelihood.device_mixture(e), self._log_prior.device_mixture(e)
+        acc = np.zeros(len(rows))
+        for r, sl in enumerate(rows):
+            mu, L, Linv, nu = refs[r]
+            e.chain_set(chains[r], t0, 1)
+            n_acc, _, states[r]["rho"] = e.pcn_mutate(z[sl], ll[sl], lp[sl], lq[sl], float(ladder[r]), mu, L, Linv, t_ll, t_lp, t_lp, seed,
+                                                      r * z[sl].shape[0], states[r]["rho"], chunk, t0, target, 1, "f64", nu)
+            acc[r] = float(np.sum(n_acc))
+        self.n_likelihood_evaluations += chunk * z.shape[0]
+        return acc
+
+    def _segment_generic(self, run, t0: int, chunk: int):
+        """Callables, and every chain in a preconditioned space: per rung the split propose / densities / accept loop of
+        `HipMiniPCN._steps_generic` at beta_r with lq' := lp', recorded from the rows."""
+        e = self.engine
+        z, logj, ll, lp, lq, T, rows, ladder, states, refs, seed, target, chains = run
+        builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
+        self.last_mutation_path = ("preconditioned chain (z = T(x)): " if T is not None else "") + \
+            ("built-in densities by their own kernel: " if builtin else "callables: ") + \
+            "per rung split propose / accept at beta_r (asmc_pcn_split_*), recorded from the rows; exchange by asmc_pt_swap"
+        acc = np.zeros(len(rows))
+        for r, sl in enumerate(rows):
+            mu, L, Linv, nu = refs[r]
+            zr, llr, lpr, lqr = z[sl], ll[sl], lp[sl], lq[sl]
+            logjr = None if logj is None else logj[sl]
+            n = zr.shape[0]
+            e.pcn_split_begin(states[r]["rho"])
+            for t in range(t0, t0 + chunk):
+                z_prop, q0, q1 = e.pcn_propose(zr, mu, L, Linv, 0.0, seed, r * n, t, nu=nu)
+                ll_new, lp_new, _, logj_new = self._densities(z_prop, T, lqr)
+                e.pcn_accept(zr, z_prop, llr, lpr, lqr, ll_new, lp_new, lp_new, q0, q1, float(ladder[r]), seed, r * n, t,
+                             logj_old=logjr, logj_new=logj_new, want_count=False)
+                e.pcn_split_adapt(n, target, t - t0, True)
+                self._record(chains[r], t, zr, llr, lpr, T)
+            n_acc, _, states[r]["rho"] = e.pcn_split_end(chunk)
+            acc[r] = float(np.sum(n_acc))
+        return acc

@@ -410,6 +410,14 @@ class MCMCSamples(BaseSamples):
     def _meta(self) -> dict:
         return dict(thin=self.thin, burn_in=self.burn_in, autocorrelation_time=self.autocorrelation_time)
 
+    def _post_process_index(self, burn_in: int, thin: int):
+        """What `post_process` indexes the chain with: the step axis is the first one here."""
+        return slice(burn_in, None, thin)
+
+    def _extra_kwargs(self, conv=None) -> dict:
+        """Constructor arguments of a subclass that travel through post_process / to_numpy / to_namespace."""
+        return {}
+
     def post_process(self, burn_in: int = 0, thin: int = 1) -> "MCMCSamples":
         """Drop the first `burn_in` steps and keep every `thin`-th of the rest; the metadata accumulate (thin multiplies,
         burn_in adds).  Nothing to do returns this object itself."""
@@ -420,7 +428,7 @@ class MCMCSamples(BaseSamples):
         if burn_in == 0 and thin == 1:
             logger.warning("No burn-in or thinning applied, returning original samples")
             return self
-        keep = slice(burn_in, None, thin)
+        keep = self._post_process_index(burn_in, thin)
         chain = self.chain[keep]
         per_row = lambda v: None if v is None else v.reshape(self.chain_shape)[keep].reshape(-1)  # noqa: E731
         return self.__class__(x=chain.reshape(-1, self.dims), log_likelihood=per_row(self.log_likelihood),
@@ -428,7 +436,7 @@ class MCMCSamples(BaseSamples):
                               device=self.device, dtype=self.dtype, chain_shape=tuple(chain.shape[:-1]),
                               thin=thin if self.thin is None else self.thin * thin,
                               burn_in=burn_in if self.burn_in is None else self.burn_in + burn_in,
-                              autocorrelation_time=self.autocorrelation_time)
+                              autocorrelation_time=self.autocorrelation_time, **self._extra_kwargs())
 
     def __getitem__(self, idx):
         sliced = super().__getitem__(idx)  # (chain_shape = None: the rows left are one flat chain)
@@ -439,14 +447,15 @@ class MCMCSamples(BaseSamples):
         conv = lambda v: None if v is None else to_numpy(v)  # noqa: E731
         return self.__class__(x=to_numpy(self.x), parameters=self.parameters, log_likelihood=conv(self.log_likelihood),
                               log_prior=conv(self.log_prior), log_q=conv(self.log_q), xp=np, chain_shape=self.chain_shape,
-                              thin=self.thin, burn_in=self.burn_in, autocorrelation_time=conv(self.autocorrelation_time))
+                              thin=self.thin, burn_in=self.burn_in, autocorrelation_time=conv(self.autocorrelation_time),
+                              **self._extra_kwargs(conv))
 
     def to_namespace(self, xp, dtype=None):
         dev = self.device if is_torch_namespace(xp) else None
         conv = lambda v: None if v is None else asarray(v, xp, device=dev)  # noqa: E731
         return self.__class__(x=conv(self.x), parameters=self.parameters, log_likelihood=conv(self.log_likelihood),
                               log_prior=conv(self.log_prior), log_q=conv(self.log_q), xp=xp, dtype=dtype, chain_shape=self.chain_shape,
-                              **self._meta())
+                              **self._meta(), **self._extra_kwargs(conv))
 
     def _encode_for_hdf5(self, flat: bool = True) -> dict:
         d = super()._encode_for_hdf5(flat=flat)
@@ -454,6 +463,197 @@ class MCMCSamples(BaseSamples):
         if d.get("autocorrelation_time") is not None:
             d["autocorrelation_time"] = to_numpy(d["autocorrelation_time"])
         return d
+
+
+_trapezoid = getattr(np, "trapezoid", None) or np.trapz
+
+
+@dataclass
+class PTMCMCSamples(MCMCSamples):
+    """samples.py:810-1205 (without plotting) - the container of the "pt_minipcn" sampler.  A parallel-tempered chain
+    [n_temps, n_steps, n_walkers, d] lies flattened in `x` like any chain; `betas` [n_temps] is the ladder, 1 first and strictly
+    decreasing.  The two evidence estimators return what the reference returns, NaN and -inf propagation included: on numpy arrays
+    by host arithmetic in the reference's order, on device tensors from the reductions of `asmc_pt_evidence` with
+    only the scalar arithmetic on the host."""
+
+    betas: Any | None = None
+    engine: Any = field(default=None, repr=False, compare=False)
+
+    def __post_init__(self):
+        super().__post_init__()
+        if self.betas is not None:
+            self.betas = self.array_to_namespace(self.betas, dtype=self._scalar_dtype())  # (fp64 on the device: SURVEY.md H7)
+            if self.betas.ndim != 1:
+                raise ValueError("betas must be a 1D array")
+            if len(self.betas) != self.n_temps:
+                raise ValueError("Length of betas must match the number of temperatures in the chain")
+            if not bool(self.betas[0] == 1):
+                raise ValueError("betas must start at 1")
+            if not bool((self.betas[1:] - self.betas[:-1] < 0).all()):
+                raise ValueError("betas must be in decreasing order")
+
+    @classmethod
+    def from_chain(cls, chain, betas=None, log_likelihood=None, log_prior=None, log_q=None, parameters=None, xp=None, dtype=None,
+                   device=None, thin: int | None = None, burn_in: int | None = None, autocorrelation_time=None, **extra):
+        """A chain [n_temps, ..., d] (commonly [n_temps, n_steps, n_walkers, d]) and its ladder."""
+        if getattr(chain, "ndim", np.ndim(chain)) < 3:
+            raise ValueError("chain must have at least 3 dimensions")
+        return super().from_chain(chain, log_likelihood=log_likelihood, log_prior=log_prior, log_q=log_q, parameters=parameters, xp=xp,
+                                  dtype=dtype, device=device, thin=thin, burn_in=burn_in, autocorrelation_time=autocorrelation_time,
+                                  betas=betas, **extra)
+
+    @property
+    def n_temps(self) -> int:
+        return self.chain_shape[0]
+
+    def _post_process_index(self, burn_in: int, thin: int):
+        return (slice(None), slice(burn_in, None, thin))  # the step axis is the second one
+
+    def _extra_kwargs(self, conv=None) -> dict:
+        return {"betas": self.betas if conv is None or self.betas is None else conv(self.betas)}
+
+    def _per_row(self, v):
+        return None if v is None else v.reshape(self.chain_shape)
+
+    def at_temperature(self, index: int) -> MCMCSamples:
+        """Rung `index` as a plain MCMCSamples."""
+        pick = lambda v: None if v is None else self._per_row(v)[index]  # noqa: E731
+        tau = self.autocorrelation_time
+        return MCMCSamples.from_chain(chain=self.chain[index], log_likelihood=pick(self.log_likelihood), log_prior=pick(self.log_prior),
+                                      log_q=pick(self.log_q), parameters=self.parameters, xp=self.xp, dtype=self.dtype,
+                                      device=self.device, thin=self.thin, burn_in=self.burn_in,
+                                      autocorrelation_time=None if tau is None else tau[index])
+
+    def cold_chain(self) -> MCMCSamples:
+        return self.at_temperature(0)
+
+    def subsample(self, n_samples_per_temperature: int, rng=None) -> "PTMCMCSamples":
+        """`n_samples_per_temperature` rows of every rung, drawn without replacement, each rung on its own."""
+        rng = np.random.default_rng() if rng is None else rng
+        per_temp = math.prod(self.chain_shape[1:])
+        if n_samples_per_temperature > per_temp:
+            raise ValueError(f"n_samples_per_temperature ({n_samples_per_temperature}) exceeds available samples per temperature "
+                             f"({per_temp})")
+        picks = [rng.choice(per_temp, size=n_samples_per_temperature, replace=False) for _ in range(self.n_temps)]
+        if is_torch_namespace(self.xp):
+            idx = torch.as_tensor(np.stack(picks), device=self.x.device)
+            take = lambda v, tail: torch.gather(v.reshape(self.n_temps, per_temp, *tail), 1,  # noqa: E731
+                                                idx.reshape(*idx.shape, *([1] * len(tail))).expand(*idx.shape, *tail))
+        else:
+            idx = np.stack(picks)
+            take = lambda v, tail: np.take_along_axis(v.reshape(self.n_temps, per_temp, *tail),  # noqa: E731
+                                                      idx.reshape(*idx.shape, *([1] * len(tail))), axis=1)
+        opt = lambda v: None if v is None else take(v, ())  # noqa: E731
+        return self.__class__.from_chain(chain=take(self.x, (self.dims,)), betas=self.betas, log_likelihood=opt(self.log_likelihood),
+                                         log_prior=opt(self.log_prior), log_q=opt(self.log_q), parameters=self.parameters, xp=self.xp,
+                                         dtype=self.dtype, device=self.device, **self._meta())
+
+    def __getitem__(self, idx):
+        raise NotImplementedError("Slicing is not supported for PTMCMCSamples. Use at_temperature() to extract samples at a specific "
+                                  "temperature.")
+
+    def _encode_for_hdf5(self, flat: bool = True) -> dict:
+        d = super()._encode_for_hdf5(flat=flat)
+        if d.get("betas") is not None:
+            d["betas"] = to_numpy(d["betas"])
+        return d
+
+    # ---- evidence -------------------------------------------------------------------------------------------------------
+    def _kept(self, burn_in_fraction):
+        """(log-likelihood [n_temps, n_steps, ...], first kept step)"""
+        ll = self._per_row(self.log_likelihood)
+        return ll, (int(ll.shape[1] * burn_in_fraction) if burn_in_fraction is not None else 0)
+
+    def _on_device(self) -> bool:
+        return is_torch(self.log_likelihood) and self.log_likelihood.device.type == "cuda"
+
+    def _device_stats(self, istart: int):
+        """asmc_pt_evidence over the kept steps: (n, sums [T], max / S1 / S2 [T] of the stepping stones, TI (mean, M2))."""
+        e = self.engine if self.engine is not None else get_default_engine()
+        betas = np.asarray(to_numpy(self.betas), dtype=np.float64)
+        T = len(betas)
+        stride = math.prod(self.chain_shape[1:])
+        offset = istart * math.prod(self.chain_shape[2:])
+        # trapezoid weights of the ascending ladder, per rung of the stored (descending) order: half the distance to each neighbour
+        c = np.zeros(T)
+        c[:-1] += 0.5 * (betas[:-1] - betas[1:])
+        c[1:] += 0.5 * (betas[:-1] - betas[1:])
+        s = np.zeros(T)
+        s[1:] = betas[:-1] - betas[1:]
+        out = e.pt_evidence(self.log_likelihood, T, stride, offset, stride - offset, np.stack([c, s]))
+        return stride - offset, out[:T, 0], out[:T, 1], out[:T, 2], out[:T, 3], out[T, 1], out[T, 2]
+
+    def log_evidence_thermodynamic_integration(self, burn_in_fraction: float | None = 0.1, method: str = "variance"):
+        """(log Z, error) by thermodynamic integration: the trapezoid of the rungs' mean log-likelihood over beta (Annis et al.
+        2019, doi 10.1016/j.jmp.2019.01.005, section 2.1.3).  method "variance": the standard error of the per-sample trapezoids
+        (eq. 36-37); "coarse": the difference to the trapezoid over every other rung (ptemcee's estimate)."""
+        if self.betas is None:
+            raise ValueError("Betas must be provided to compute evidence")
+        ll, istart = self._kept(burn_in_fraction)
+        if math.prod(ll.shape[2:]) * (ll.shape[1] - min(istart, ll.shape[1])) == 0:
+            raise ValueError("No samples available after burn-in for TI evidence")
+        ti_var = None
+        if self._on_device():
+            n, sums, _, _, _, _, ti_m2 = self._device_stats(istart)
+            betas = np.asarray(to_numpy(self.betas), dtype=np.float64)[::-1]
+            means = (sums / n)[::-1]
+            ti_var = ti_m2 / n
+        else:
+            lls = np.asarray(to_numpy(ll))[:, istart:]
+            lls = lls.reshape(lls.shape[0], -1)
+            order = np.argsort(to_numpy(self.betas))
+            betas, lls = np.asarray(to_numpy(self.betas))[order], lls[order]
+            means = np.mean(lls, axis=1)
+            n = lls.shape[1]
+        log_z = _trapezoid(means, betas)
+        if method == "variance":
+            if ti_var is None:
+                ti_var = np.var(_trapezoid(lls, betas, axis=0))
+            err = math.sqrt(float(ti_var / n))
+        elif method == "coarse":
+            b, m = betas[::-1], means[::-1]
+            if b[-1] != 0:
+                logger.warning("Hottest chain is not at beta=0, duplicating hottest chain with beta=0 for error estimation")
+                b2, m2 = np.concatenate((b[::2], [0])), np.concatenate((m[::2], [m[-1]]))
+            else:
+                b2, m2 = np.concatenate((b[:-1:2], [0])), np.concatenate((m[:-1:2], [m[-1]]))
+            err = abs(log_z - (-_trapezoid(m2, b2)))
+        else:
+            raise ValueError(f"Invalid method for log evidence error estimation: {method}")
+        return float(log_z), float(err)
+
+    def log_evidence_stepping_stone(self, burn_in_fraction: float | None = 0.1):
+        """(log Z, error) by the stepping-stone estimator (Annis et al. 2019, section 2.2.3): log Z = sum over adjacent rungs of
+        log mean exp((beta_j - beta_{j+1}) log L) under the hotter rung (eq. 51), error from eq. 53.  The ladder must end at 0."""
+        if self.betas is None:
+            raise ValueError("Betas must be provided to compute evidence")
+        if self.betas[-1] != 0:
+            raise ValueError("Stepping stone estimator requires the hottest chain to be at beta=0")
+        ll, istart = self._kept(burn_in_fraction)
+        if math.prod(ll.shape[2:]) * (ll.shape[1] - min(istart, ll.shape[1])) == 0:
+            raise ValueError("No samples available after burn-in for stepping-stone evidence")
+        log_z, var = 0.0, 0.0
+        if self._on_device():
+            n, _, a_max, s1, s2, _, _ = self._device_stats(istart)
+            for j in range(1, len(a_max)):
+                mean_shift = float(s1[j] / n)
+                log_z += math.log(mean_shift) + float(a_max[j])
+                var += float(s2[j] / mean_shift**2)
+        else:
+            lls = np.asarray(to_numpy(ll))[:, istart:]
+            lls = lls.reshape(lls.shape[0], -1)
+            order = np.argsort(to_numpy(self.betas))[::-1]
+            betas, lls = np.asarray(to_numpy(self.betas))[order], lls[order]
+            n = lls.shape[1]
+            for j in range(len(betas) - 1):
+                a = (betas[j] - betas[j + 1]) * lls[j + 1]
+                a_max = np.max(a)
+                shifted = np.exp(a - a_max)
+                mean_shift = float(np.mean(shifted))
+                log_z += math.log(mean_shift) + float(a_max)
+                var += float(np.sum((shifted / mean_shift) ** 2))
+        var /= n**2
+        return float(log_z), math.sqrt(float(var))
 
 
 @dataclass

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 28
+#define ASMC_ABI_VERSION 29
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -983,6 +983,43 @@ int asmc_chain_record(asmc_ctx* ctx, const asmc_chain_target* chain, int64_t slo
                       asmc_stream stream);
 int asmc_chain_set(asmc_ctx* ctx, const asmc_chain_target* chain);
 int asmc_chain_clear(asmc_ctx* ctx);
+
+/* ---- parallel tempering of the "pt_minipcn" sampler (ABI 29) ----------------------------------------
+ * State: T rungs of W walkers, row-major x_dev [T W, d] of x_dtype with rung r in rows r W .. (r + 1) W, the carried
+ * ll_dev / lp_dev [T W] (fp64) and up to two optional fp64 companions c0_dev / c1_dev [T W] that travel with a row (the lq := lp
+ * mirror, log|det J| of a preconditioned chain; either may be NULL).  betas_dev [T] (fp64, device): the ladder.
+ *
+ * asmc_pt_swap: replica exchange round `round`.  The pairs are the rungs (r, r + 1) with r = round (mod 2), r + 1 < T; walker w
+ * of rung r meets walker w of rung r + 1.  The pair exchanges rows and carried values iff both log-likelihoods are finite and
+ *     log u < (beta_r - beta_{r+1}) * (ll[r+1, w] - ll[r, w])       (fp64, this association)
+ * so a NaN or an infinity on either side never moves (the rule of the step kernels for +inf: it never settles in a colder
+ * rung).  u = U(words 0, 1) of the Philox4x32-10 block with counter {w lo, w hi, round, 0x50000000 | r} and key {seed lo, seed
+ * hi}, U the 53-bit uniform of the pCN accept stream ((k + 1/2) 2^-53), log u by the noise generator's log.  Word 3 = 0x50000000 |
+ * r is used by no other stream of the library under the same key: the pCN noise has q | 0x20000000 and q | 0x40000000
+ * (q < 2^28) there, the Gamma variates 0x80000000 | a and 0xC0000000 | a, the accept uniform 0xFFFFFFFF, the stretch move
+ * 0x60000000 | shard and 0xA0000000 | shard, NUTS 0x60000000 | k.
+ * Every lane that moves a piece of a row recomputes the decision from the same counters (the lanes of one pair sit in one wave
+ * and read both log-likelihoods before any of them writes); an accepted row moves as 16-byte vectors where d * sizeof(T) and
+ * x_dev allow, element-wise otherwise.  counts_dev [T - 1] (int64, device) += accepted walkers of pair (r, r + 1): block
+ * partials in LDS, then at most one atomic per block and pair.  Unpaired rungs and rows beyond T W are never touched.  Only
+ * enqueues: no host synchronisation, no allocation.
+ *
+ * asmc_pt_evidence: the reductions behind PTMCMCSamples.log_evidence_thermodynamic_integration / _stepping_stone (reference
+ * samples.py:1013-1170) over a recorded log-likelihood chain ll_dev [T, stride] (fp64): rung r's kept samples are the n values
+ * from ll_dev + r * stride + offset (offset + n <= stride).  coef_dev [2, T] (fp64, device): c_r, the trapezoid's weight of rung
+ * r, and s_r, the scale of rung r in the stepping-stone ratio (beta_{r-1} - beta_r; s_0 is not used).  out_dev [T + 1, 4]
+ * (fp64, device):
+ *     row r < T   {sum_i ll[r, i],  max_i a_i,  sum_i exp(a_i - max),  sum_i exp(2 (a_i - max))},  a_i = s_r * ll[r, i]
+ *     row T       {n,  mean_i ti_i,  sum_i (ti_i - mean)^2,  0},  ti_i = sum_r c_r * ll[r, i] (r ascending)
+ * The sums over exp merge (max, sum) pairs; an infinite maximum gives NaN sums, as numpy's exp(a - max(a)) does, and a NaN
+ * anywhere gives NaN.  The centred second moment is a Welford / Chan pairwise merge across lanes, waves and blocks - a constant
+ * chain gives exactly 0.  Two launches on the stream, no synchronisation: the caller copies out_dev. */
+#define ASMC_PT_MAX_RUNGS 64
+int asmc_pt_swap(asmc_ctx* ctx, int n_temps, int64_t n_walkers, int d, int x_dtype, void* x_dev, double* ll_dev, double* lp_dev,
+                 double* c0_dev, double* c1_dev, const double* betas_dev, uint64_t seed, uint32_t round, int64_t* counts_dev,
+                 asmc_stream stream);
+int asmc_pt_evidence(asmc_ctx* ctx, int n_temps, int64_t stride, int64_t offset, int64_t n, const double* ll_dev,
+                     const double* coef_dev, double* out_dev, asmc_stream stream);
 
 #ifdef __cplusplus
 }
