@@ -201,7 +201,7 @@ int asmc_ctx_create(asmc_ctx** ctx_out, int device, int64_t n_max, int d_max) {
     dmalloc((void**)&c->d_mmtab, sizeof(double) * 2 * 144 * 64);
     dmalloc((void**)&c->d_guide, sizeof(unsigned int) * ((size_t)n_max + 8));
     // the fused flow step's counters sit directly in FRONT of the flag bytes: one memset clears both (asmc_pcn_mutate_flow)
-    dmalloc((void**)&c->d_tilectr, ASMC_TILECTR_BYTES + (size_t)n_max + 64);
+    dmalloc((void**)&c->d_tilectr, ASMC_TILECTR_BYTES + scratch_flags_len(n_max));  // (the flag bytes' users: asmc_scratch.h)
     c->d_flags = c->d_tilectr ? reinterpret_cast<unsigned char*>(c->d_tilectr) + ASMC_TILECTR_BYTES : nullptr;
     dmalloc((void**)&c->d_gamma, sizeof(double) * ((size_t)ASMC_GAMMA_BATCH * (size_t)n_max + 64 * ASMC_GAMMA_BATCH));
     dmalloc((void**)&c->d_rec, sizeof(double) * 4 * (size_t)n_max);

@@ -467,9 +467,15 @@ __device__ __forceinline__ void soa_store(__amdgpu_buffer_rsrc_t r, unsigned vof
 bool asmc_pcn_flow_fused_ok(const asmc_pcn_params* prm, const asmc_coupling* f);
 int asmc_pcn_flow_fused_launch(asmc_ctx* ctx, int64_t n, int x_dtype, double* ll, double* lp, double* lq, const PcnDev& pd,
                                const asmc_coupling* f, const double* rho_ptr, uint32_t step, unsigned int* tile_counter,
-                               long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, int img_words, hipStream_t st);
+                               long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, int img_words, bool no_density,
+                               hipStream_t st);
 // the steps' LDS image, once per mutation call (asmc_pcn_fused.hip); *words_out goes to asmc_pcn_flow_fused_launch
 int asmc_pcn_flow_fused_stage(asmc_ctx* ctx, const PcnDev& pd, const asmc_coupling* f, int* words_out, hipStream_t st);
+// beta = 1 exactly: the steps run without the flow density (no_density; accepting lanes mark the bytes behind ctx->d_flags' tile parities, zeroed by the call) and
+// one refresh behind the last of them stores log q of the particles that moved; _beta1_ok: whether the call can run that way
+bool asmc_pcn_flow_fused_beta1_ok(const asmc_coupling* f, int img_words);
+int asmc_pcn_flow_fused_refresh(asmc_ctx* ctx, int64_t n, int x_dtype, double* lq, const PcnDev& pd, const asmc_coupling* f,
+                                const double* rho_ptr, unsigned long long* nonfinite, hipStream_t st);
 
 // d = 64 / 128 pCN on the fp64 matrix cores (asmc_pcn_mm.hip)
 #define MM_WHITEN 0

@@ -642,11 +642,18 @@ static int pcn_mutate_flow_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, d
             // (sizes in multiples of 16 bytes: a ragged memset is two fill kernels)
             // ... and every tile starts in half 0 of the state allocation (tile parities: the split path's flag bytes,
             // free here, which sit right behind the counters: ONE fill)
-            ASMC_HIP(hipMemsetAsync(ctx->d_tilectr, 0, ASMC_TILECTR_BYTES + ((size_t)((n + 63) / 64) + 15) / 16 * 16, st));
+            // (beta = 1: the call's `moved` marks, one per PARTICLE, lie behind the parities - asmc_scratch.h - and the fill reaches
+            // over them as well)
+            const bool at_one = prm->beta == 1.0;
+            ASMC_HIP(hipMemsetAsync(ctx->d_tilectr, 0, ASMC_TILECTR_BYTES + scratch_flags_moved_off(n) + (at_one ? scratch_flags_fill(n) : 0), st));
             pd.tile_par = ctx->d_flags;
             int img_words = 0;  // the steps' LDS image, built once per call (0: every step stages for itself)
             rc = asmc_pcn_flow_fused_stage(ctx, pd, flow, &img_words, st);
             if (rc) return rc;
+            // beta = 1 EXACTLY: (1 - beta) lq + beta (ll + lp) is 0 * lq + (ll + lp), no accept decision reads the flow density - the
+            // steps run without it and one refresh behind the last of them stores log q of the particles that moved
+            // (asmc_pcn_fused.hip, FUSED_MODE_NQ / _LQ).  Any other beta, however close: the full step.
+            const bool no_density = at_one && asmc_pcn_flow_fused_beta1_ok(flow, img_words);
             const int lag = prm->adapt >= 2 ? prm->adapt : 1;
             rc = pcn_steps(
                 loop, pd,
@@ -663,7 +670,7 @@ static int pcn_mutate_flow_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, d
                         return ASMC_ERR_ARG;
                     }
                     return asmc_pcn_flow_fused_launch(ctx, n, prm->x_dtype == ASMC_F64 ? ASMC_F64 : ASMC_F32, ll, lp, lq, pd, flow, d_rho, step,
-                                                      ctx->d_tilectr + t, d_block, g, ad, img_words, st);
+                                                      ctx->d_tilectr + t, d_block, g, ad, img_words, no_density, st);
                 },
                 [&](int t, int) -> int {
                     // the kernel's last block left this rank's count in the step's cell: exchange it - lagged runs at the end of a block
@@ -676,6 +683,10 @@ static int pcn_mutate_flow_impl(asmc_ctx* ctx, int64_t n, void* x, double* ll, d
                     // nobody's prologue follows the last step
                     return t == n_steps - 1 ? pcn_adapt_exchanged_launch(ctx, t, prm->target_accept, prm->adapt, lag, st) : ASMC_OK;
                 });
+            // (in front of the un-whitening and the call's tail: the NaN census of the carried log q and a deferred call's result
+            // see the refreshed values)
+            if (!rc && no_density)
+                rc = asmc_pcn_flow_fused_refresh(ctx, n, prm->x_dtype == ASMC_F64 ? ASMC_F64 : ASMC_F32, lq, pd, flow, d_rho, pcn_flow_bad_cell(ctx), st);
         } else {
             rc = pcn_steps(
                 loop, pd,

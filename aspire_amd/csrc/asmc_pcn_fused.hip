@@ -238,16 +238,33 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_fused_stage_image(const doubl
 // mat-vec accumulators alive past the first quadratic forms, and compiled into the single-Gaussian kernel it cost the headline
 // 90 spilled registers (0.294 -> 0.320 ms per step).
 // img / img_words: the call's LDS image (fused_stage_tables) and its size in 16-byte words; img == nullptr: staged here
-template <typename T, int W, int NOISE, bool HS, int KIND = ASMC_FLOW_COUPLING, bool MIX = false>
-__global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
+//
+// MODE: the step has three forms, one body (the kernels below are thin wrappers around it).
+//   FUSED_MODE_STEP  the step described above.
+//   FUSED_MODE_NQ    the step without the proposal density, for beta = 1 exactly: there the tempered target is 0 * lq + (ll + lp) and
+//                    log q cannot move an accept decision.  Phase 1 and the accept prelude as they are, no flow; an accepting lane
+//                    stores ll, lp, the placeholder lq = +0 (finite: a carried NaN must not outlive the move, its log_p_t is -inf
+//                    and would accept everything from then on) and moved[i] = 1.  Independent of the flow: LDS holds the tables and
+//                    the Box-Muller part of the image alone (they start at word 0 here).
+//   FUSED_MODE_LQ    the refresh behind the last such step: log q of the stored y for the particles that moved, by this body's own
+//                    transposes, mat-vec, rounding, standardisation, lane swaps and layer calls - y is exactly the y' the registers
+//                    of the accepting step held, so the value is the one FUSED_MODE_STEP would have stored, bit for bit.  A
+//                    particle that never moved keeps the log q it came in with.  Writes lq of moved particles, nothing else.
+#define FUSED_MODE_STEP 0
+#define FUSED_MODE_NQ 1
+#define FUSED_MODE_LQ 2
+template <typename T, int W, int NOISE, bool HS, int KIND, bool MIX, int MODE>
+__device__ __forceinline__ void fused_step_body(
     int64_t n, double* __restrict__ ll, double* __restrict__ lp, double* __restrict__ lq, const double* __restrict__ ptab,
     PcnScalars p, const double* rho_ptr, uint32_t step, const float* __restrict__ packed, int n_layers,
     const float* __restrict__ loc, const float* __restrict__ scale, float ladj0, float base_const,
     unsigned int* __restrict__ tile_counter, long long* __restrict__ block_counts, PcnAdaptArgs ad, int par_words, int affine,
-    const fused_u4* __restrict__ img, int img_words) {
+    const fused_u4* __restrict__ img, int img_words, unsigned char* __restrict__ moved) {
     constexpr int D = FUSED_D, H = 16, THREADS = FUSED_THREADS;
     constexpr int HF = KIND == ASMC_FLOW_MAF ? 32 : H;  // H of the flow's layer templates (lane halves hold HF / 2 inputs)
     static_assert(KIND == ASMC_FLOW_COUPLING || HS, "the autoregressive variant runs the split-fp16 layers only");
+    static_assert(MODE == FUSED_MODE_STEP || (FUSED_MVMFMA && FUSED_INPLACE), "the beta = 1 modes live in the matrix-core, in-place build");
+    static_assert(MODE != FUSED_MODE_LQ || HS, "the refresh runs the split-fp16 layers");
     using FD = FlowDims<HF, W>;
     extern __shared__ __align__(16) float sp[];
     // The image arrives in ONE sweep: every thread issues all of its 16-byte loads (IMG_Q: a CU's whole LDS over the block), then
@@ -255,18 +272,21 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
     // trip of each of its loops, and no conversion, no division, no index arithmetic in front of the first tile.  (The parity
     // snapshot of the two-halves build below changes from launch to launch and stays here.  Issuing the first tile's state loads
     // in front of the landing as well was tried: in either order the tile loop then spilled 36 - 40 bytes of registers, so it is not done.)
-    constexpr int IMG_Q = ASMC_FUSED_IMAGE_BYTES / 16 / THREADS;
+    // (the step without the density is handed the image from its tables on: 17 KB, three words per thread; the beta = 1 modes
+    // always run from an image)
+    constexpr int IMG_BYTES = MODE == FUSED_MODE_NQ ? (int)(FUSED_TL_DOUBLES * sizeof(double) + BM_TAB_N * sizeof(bm_d2)) : ASMC_FUSED_IMAGE_BYTES;
+    constexpr int IMG_Q = (IMG_BYTES / 16 + THREADS - 1) / THREADS;
     fused_u4 iw[IMG_Q];
-    if (img != nullptr) {
+    if (MODE != FUSED_MODE_STEP || img != nullptr) {
 #pragma unroll
         for (int q = 0; q < IMG_Q; q++) {
             const int i4 = q * THREADS + (int)threadIdx.x;
             iw[q] = img[i4 < img_words ? i4 : img_words - 1];  // (rows beyond the image re-read its last word and store nothing)
         }
-    } else {
+    } else if constexpr (MODE == FUSED_MODE_STEP) {
         fused_stage_tables<W, NOISE, HS, KIND>(sp, ptab, p, packed, n_layers, loc, scale);
     }
-    double* tl = reinterpret_cast<double*>(sp + (size_t)n_layers * FD::LAYER);
+    double* tl = reinterpret_cast<double*>(sp + (MODE == FUSED_MODE_NQ ? (size_t)0 : (size_t)n_layers * FD::LAYER));
     bm_d2* bmt = reinterpret_cast<bm_d2*>(tl + FUSED_TL_DOUBLES);
     // ... and the tiles' parity bits (below), one bit per tile, when they fit (par_words > 0): a snapshot is all a launch
     // needs - a tile is read once per launch, before its own wave may flip it
@@ -282,7 +302,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
         }
         par_bits[wd] = bits;
     }
-    if (img != nullptr) {
+    if (MODE != FUSED_MODE_STEP || img != nullptr) {
         __builtin_amdgcn_sched_barrier(0);  // (every load above is issued before the first wait)
 #pragma unroll
         for (int q = 0; q < IMG_Q; q++) {
@@ -384,7 +404,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
     const unsigned n_dealt = (unsigned)(((n + 63) / 64) / deal_stride) * deal_stride;
     unsigned deal_next = blockIdx.x * (unsigned)(THREADS / 64) + (threadIdx.x >> 6);
     auto tile_fetch = [&]() -> unsigned {
-        if (deal_next < n_dealt) {  // (wave uniform)
+        if (MODE == FUSED_MODE_LQ || deal_next < n_dealt) {  // (wave uniform; the refresh deals every tile: it has no counter of its own)
             const unsigned t_d = deal_next;
             deal_next += deal_stride;
             return t_d;
@@ -410,7 +430,9 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
 #pragma unroll
         for (int j = 0; j < D; j++) v[j] = soa_load<T>(ysr, ys_lane, ys_tile + (unsigned)j * ys_row);
         oll = olp = olq = 0.0;
-        if (valid) oll = ll[i], olp = lp[i], olq = lq[i];
+        if constexpr (MODE != FUSED_MODE_LQ) {
+            if (valid) oll = ll[i], olp = lp[i], olq = lq[i];
+        }
     };
     double v[D];
     double oll = 0.0, olp = 0.0, olq = 0.0;
@@ -419,10 +441,21 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
     bool have = (int64_t)t < n_tiles;
     if (have) {
         par = tile_parity(t);
-        tile_load(t, par, v, oll, olp, olq);
+        if constexpr (MODE != FUSED_MODE_LQ) tile_load(t, par, v, oll, olp, olq);  // (the refresh loads a tile once it knows that somebody in it moved)
     }
     while (have) {
         STAMP(0);
+        bool lq_mine = false;  // the refresh: this lane's particle moved during the call
+        if constexpr (MODE == FUSED_MODE_LQ) {
+            const int64_t i_m = (int64_t)t * 64 + lane;
+            lq_mine = i_m < n && moved[i_m] != 0;
+            if (__ballot(lq_mine) == 0ull) {  // nobody of this tile moved: its log q stays as it is
+                t = (unsigned)__builtin_amdgcn_readfirstlane((int)tile_fetch());
+                have = (int64_t)t < n_tiles;
+                continue;
+            }
+            tile_load(t, par, v, oll, olp, olq);
+        }
         // the tables are loop invariant: an offset LLVM cannot see through keeps their reads inside the tile loop (hoisted,
         // they would need a thousand registers)
         // (a VECTOR register: one base address + 16-bit immediate offsets reach every table entry; with a scalar offset the
@@ -443,12 +476,13 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
         // made the tile's first instruction wait for ALL 32 state loads - they now land behind the first noise quads.  Only the
         // Student-t reference needs the sum before the first proposal coordinate (its scale depends on it).
         double q0 = 0.0, q1 = 0.0, q0t = 0.0;
-        if (p.gam != nullptr) {  // (tpcn_scale's own test)
+        if (MODE != FUSED_MODE_LQ && p.gam != nullptr) {  // (tpcn_scale's own test)
 #pragma unroll
             for (int j = 0; j < D; j++) q0t = fma(v[j], v[j], q0t);
         }
         STAMP(1);
-        const double rs = tpcn_scale(rho, p.nu, q0t, p.gam, valid ? i : 0);
+        double rs = 0.0;  // (the refresh proposes nothing: y' = y)
+        if constexpr (MODE != FUSED_MODE_LQ) rs = tpcn_scale(rho, p.nu, q0t, p.gam, valid ? i : 0);
         // The real dimension of a zero-padded problem (dn < D) is a RUN-TIME uniform: tested per quad it is two branches per quad and, where
         // the paths meet, copies of the running sums and of the quad's coordinates (six 64-bit moves per quad in the generated code of
         // round 5) - and every branch ends a scheduling region.  One branch per tile instead: the full-width loop carries no test at all
@@ -487,8 +521,10 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
                 }
             }
         };
-        if (dn == D) noise_phase(std::true_type{});
-        else noise_phase(std::false_type{});
+        if constexpr (MODE != FUSED_MODE_LQ) {
+            if (dn == D) noise_phase(std::true_type{});
+            else noise_phase(std::false_type{});
+        }
         STAMP(2);
         // x'_j = mu_j + sum_k L[j,k] y'_k, four rows at a time: straight into the targets' quadratic forms and into the
         // flow's standardised fp32 input (the same (float) x' and division the stand-alone flow kernel applies)
@@ -716,13 +752,15 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
         // doubles fewer alive across the flow (the kernel sits at the 256-register edge: they were spills); the re-association moves
         // a decision only where its margin is within an ulp or two of the sum (the razor edges the parity tests allow for)
         double kacc = ((t2 + c1) - rhs) - logu;
-        asm volatile("" : "+v"(kacc), "+v"(kll), "+v"(klp));
+        if constexpr (MODE != FUSED_MODE_LQ) asm volatile("" : "+v"(kacc), "+v"(kll), "+v"(klp));  // (the refresh decides nothing: the prelude is dead code there)
 #ifndef FUSED_NOSB
         __builtin_amdgcn_sched_barrier(0);
 #endif
         // ---- phase 2: two flow tiles (particles 0-31 and 32-63 of this wave) on the MFMA -----------------------------
-        float lqt[2];
+        float lqt[2] = {0.0f, 0.0f};
         unsigned tn_l = 0;
+        if constexpr (MODE == FUSED_MODE_NQ) tn_l = tile_fetch();  // no flow: the next tile's index alone
+        if constexpr (MODE != FUSED_MODE_NQ) {
         float xaA[1][H / 2], xbA[1][H / 2], xaB[1][H / 2], xbB[1][H / 2];
         if constexpr (MVM) {
             // lane (g, n) holds rows 4 g + r (mb = 0) and 16 + 4 g + r (mb = 1) of particles 16 nb + n.  Flow tile A = particles 0-31
@@ -901,14 +939,28 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
         }  // KIND
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(0);
+        }  // MODE != FUSED_MODE_NQ
         STAMP(6);
-        const double nlq = (double)(hh == 0 ? lqt[0] : lqt[1]);
+        // (without the density: the placeholder an accepting lane stores, +0 - FUSED_MODE_LQ replaces it behind the last step)
+        const double nlq = MODE == FUSED_MODE_NQ ? 0.0 : (double)(hh == 0 ? lqt[0] : lqt[1]);
         // ---- phase 3: accept, on the lane's own particle ---------------------------------------------------------------
         // a non-finite log q(x') (NaN, or +-inf: fp16 operand overflow at |activation| >= 65504 in the split products,
         // asmc_flow_dev.h) rejects the proposal; counted, so that the host can tell the user
         const bool lq_finite = fabs(nlq) < INFINITY;
-        if (valid && !lq_finite) n_bad++;
-        const bool accepted = valid && lq_finite && fma(1.0 - p.beta, nlq, kacc) > 0.0;  // (a NaN density compares false: rejected)
+        if constexpr (MODE == FUSED_MODE_LQ) {
+            // the moved particles' log q; a non-finite one (a proposal that beta = 1 accepted on the targets alone) is stored as it
+            // is and counted - the call's NaN census of the carried log q reports it
+            if (lq_mine) {
+                lq[i] = nlq;
+                if (!lq_finite) n_bad++;
+            }
+            t = (unsigned)__builtin_amdgcn_readfirstlane((int)tn_l);
+            have = (int64_t)t < n_tiles;
+        } else {
+        if (MODE == FUSED_MODE_STEP && valid && !lq_finite) n_bad++;
+        // (beta = 1 without the density: fma(0, lq', kacc) > 0 is kacc > 0 for every finite lq')
+        const bool accepted = MODE == FUSED_MODE_NQ ? (valid && kacc > 0.0)
+                                                    : (valid && lq_finite && fma(1.0 - p.beta, nlq, kacc) > 0.0);  // (a NaN density compares false: rejected)
 #if FUSED_INPLACE
         // y' is stored FIRST: its registers are free once the stores have issued, so the next tile's state loads into them - with
         // the loads in front (round 3's order, when y' was parked and dead by now) both tiles' rows are alive at once and the loop
@@ -917,6 +969,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
             ll[i] = kll;
             lp[i] = klp;
             lq[i] = nlq;
+            if constexpr (MODE == FUSED_MODE_NQ) moved[i] = 1;
             n_acc++;
         }
         if constexpr (MVM) {
@@ -997,6 +1050,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
         oll = olln, olp = olpn, olq = olqn;
 #pragma unroll
         for (int j = 0; j < D; j++) v[j] = vn[j];
+        }  // MODE != FUSED_MODE_LQ
     }
 #ifdef FUSED_STAMP
     if (lane == 0 && blockIdx.x == 7 && (wave == 0 || wave == 4) && ntile > 0)
@@ -1007,6 +1061,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
     n_acc = wave_sum_ll(n_acc);
     n_bad = wave_sum_ll(n_bad);
     if (lane == 0 && n_bad != 0 && ad.nonfinite) atomicAdd(ad.nonfinite, (unsigned long long)n_bad);
+    if constexpr (MODE == FUSED_MODE_LQ) return;  // (no step to close: the refresh counts nothing but those)
     if (lane == 0) s_cnt[wave] = n_acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1052,6 +1107,40 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
     }
 }
 
+// img / img_words: the call's LDS image (fused_stage_tables) and its size in 16-byte words; img == nullptr: staged here
+template <typename T, int W, int NOISE, bool HS, int KIND = ASMC_FLOW_COUPLING, bool MIX = false>
+__global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused(
+    int64_t n, double* __restrict__ ll, double* __restrict__ lp, double* __restrict__ lq, const double* __restrict__ ptab,
+    PcnScalars p, const double* rho_ptr, uint32_t step, const float* __restrict__ packed, int n_layers,
+    const float* __restrict__ loc, const float* __restrict__ scale, float ladj0, float base_const,
+    unsigned int* __restrict__ tile_counter, long long* __restrict__ block_counts, PcnAdaptArgs ad, int par_words, int affine,
+    const fused_u4* __restrict__ img, int img_words) {
+    fused_step_body<T, W, NOISE, HS, KIND, MIX, FUSED_MODE_STEP>(n, ll, lp, lq, ptab, p, rho_ptr, step, packed, n_layers, loc, scale, ladj0, base_const,
+                                                                 tile_counter, block_counts, ad, par_words, affine, img, img_words, nullptr);
+}
+// the step without the density (beta = 1).  img: the image from its pCN tables on; moved: one byte per particle, zeroed by the call
+template <typename T, int NOISE, bool MIX>
+__global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused_nq(
+    int64_t n, double* __restrict__ ll, double* __restrict__ lp, double* __restrict__ lq, PcnScalars p, const double* rho_ptr, uint32_t step,
+    unsigned int* __restrict__ tile_counter, long long* __restrict__ block_counts, PcnAdaptArgs ad, const fused_u4* __restrict__ img,
+    int img_words, unsigned char* __restrict__ moved) {
+    fused_step_body<T, 64, NOISE, true, ASMC_FLOW_COUPLING, MIX, FUSED_MODE_NQ>(n, ll, lp, lq, nullptr, p, rho_ptr, step, nullptr, 0, nullptr, nullptr, 0.0f,
+                                                                               0.0f, tile_counter, block_counts, ad, 0, 0, img, img_words, moved);
+}
+// the refresh behind the last of those steps: log q of the particles that moved.  img: the whole image (weights and pCN tables)
+template <typename T, int W, int KIND>
+__global__ __launch_bounds__(FUSED_THREADS) void k_pcn_flow_fused_lq(
+    int64_t n, double* __restrict__ lq, PcnScalars p, const double* rho_ptr, int n_layers, float ladj0, float base_const,
+    unsigned long long* __restrict__ nonfinite, int affine, const fused_u4* __restrict__ img, int img_words,
+    unsigned char* __restrict__ moved) {
+    PcnAdaptArgs ad;
+    ad.done = nullptr, ad.nonfinite = nonfinite, ad.cell = nullptr, ad.prev_cell = nullptr, ad.counts_out = nullptr, ad.rho = nullptr;
+    ad.rho_hist = nullptr, ad.target = 0.0, ad.n = n, ad.t = 0, ad.adapt = 0, ad.last = 0;
+    fused_step_body<T, W, ASMC_NOISE_F32, true, KIND, false, FUSED_MODE_LQ>(n, nullptr, nullptr, lq, nullptr, p, rho_ptr, 0u, nullptr, n_layers, nullptr,
+                                                                            nullptr, ladj0, base_const, nullptr, nullptr, ad, 0, affine, img,
+                                                                            img_words, moved);
+}
+
 // the scalars a step launch and the image builder read
 static PcnScalars fused_scalars(const PcnDev& pd) {
     PcnScalars ps;
@@ -1072,10 +1161,20 @@ static PcnScalars fused_scalars(const PcnDev& pd) {
     return ps;
 }
 
+// 16-byte word of the call's image at which the pCN tables start (behind the flow's weights: FlowDims<H, W>::LAYER floats per layer)
+static int fused_table_word0(const asmc_coupling* f) {
+    const int H = f->kind == ASMC_FLOW_MAF ? 32 : 16, W = (int)f->hidden;
+    const int layer = (2 * (W / 32) + H / 16) * 32 + W * H + W * W + 2 * H * W;
+    static_assert(FlowDims<16, 64>::LAYER == (2 * 2 + 1) * 32 + 64 * 16 + 64 * 64 + 2 * 16 * 64 && FlowDims<32, 32>::LAYER == (2 + 2) * 32 + 3 * 32 * 32 + 32 * 32,
+                  "FlowDims::LAYER by hand");
+    return (int)((size_t)f->n_layers * layer / 4);
+}
+
 template <typename T>
 static int launch_pcn_flow_fused(asmc_ctx* ctx, int64_t n, double* ll, double* lp, double* lq, const PcnDev& pd,
                                  const asmc_coupling* f, const double* rho_ptr, uint32_t step, unsigned int* tile_counter,
-                                 long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, int img_words, hipStream_t st) {
+                                 long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, int img_words, bool no_density,
+                                 hipStream_t st) {
     const PcnScalars ps = fused_scalars(pd);
     const fused_u4* img = img_words > 0 ? reinterpret_cast<const fused_u4*>(ctx->d_fimg) : nullptr;
     const float ladj0 = (float)(-f->log_scale_sum);
@@ -1083,6 +1182,30 @@ static int launch_pcn_flow_fused(asmc_ctx* ctx, int64_t n, double* ll, double* l
     const int64_t n_tiles = (n + 63) / 64;
     const int grid = (int)(n_tiles < (int64_t)ctx->num_cu * (FUSED_THREADS / 64) ? (n_tiles + FUSED_THREADS / 64 - 1) / (FUSED_THREADS / 64) : ctx->num_cu);  // one 8-wave block per CU
     *grid_out = grid;
+#if FUSED_MVMFMA && FUSED_INPLACE
+    if (no_density) {  // beta = 1 (asmc_pcn_flow_fused_beta1_ok): the same step, same label, without the flow - the image from its tables on
+        const int tab_word0 = fused_table_word0(f);
+        const size_t lds = FUSED_TL_DOUBLES * sizeof(double) + BM_TAB_N * sizeof(bm_d2);
+        const bool mix = pd.ll.C > 1 || pd.lp.C > 1;
+#define ASMC_FUSED_NQ_CASE(NZ, MX)                                                                                              \
+    if (pd.noise == NZ && mix == MX) {                                                                                          \
+        auto kern = k_pcn_flow_fused_nq<T, NZ, MX>;                                                                             \
+        ASMC_LAUNCH(ctx, st, "k_pcn_flow_fused", kern, dim3(grid), dim3(FUSED_THREADS), lds, st, n, ll, lp, lq, ps, rho_ptr,     \
+                    step, tile_counter, block_counts, adapt, img + tab_word0, img_words - tab_word0, ctx->d_flags + scratch_flags_moved_off(n)); \
+        ASMC_LAUNCH_CHECK();                                                                                                    \
+        return ASMC_OK;                                                                                                         \
+    }
+        ASMC_FUSED_NQ_CASE(ASMC_NOISE_F64, false)
+#ifndef FUSED_ONLY_HEADLINE
+        ASMC_FUSED_NQ_CASE(ASMC_NOISE_F32, false)
+        ASMC_FUSED_NQ_CASE(ASMC_NOISE_F64, true)
+        ASMC_FUSED_NQ_CASE(ASMC_NOISE_F32, true)
+#endif
+#undef ASMC_FUSED_NQ_CASE
+        asmc_set_error("fused flow step without the density: unsupported noise mode %d", (int)pd.noise);
+        return ASMC_ERR_UNSUPPORTED;
+    }
+#endif
     // flow arithmetic: split-fp16 MFMA (fp32-equivalent operands, asmc_flow_dev.h) unless ASMC_FLOW_MATH=f32 asks for the
     // fp32 MFMA chain
     // (Hidden width 128 goes through its coupling layers ONE flow tile at a time: the two interleaved tiles of coupling_layer_hs2
@@ -1214,8 +1337,82 @@ int asmc_pcn_flow_fused_stage(asmc_ctx* ctx, const PcnDev& pd, const asmc_coupli
 
 int asmc_pcn_flow_fused_launch(asmc_ctx* ctx, int64_t n, int x_dtype, double* ll, double* lp, double* lq, const PcnDev& pd,
                                const asmc_coupling* f, const double* rho_ptr, uint32_t step, unsigned int* tile_counter,
-                               long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, int img_words, hipStream_t st) {
+                               long long* block_counts, int* grid_out, const PcnAdaptArgs& adapt, int img_words, bool no_density,
+                               hipStream_t st) {
     if (x_dtype == ASMC_F64)
-        return launch_pcn_flow_fused<double>(ctx, n, ll, lp, lq, pd, f, rho_ptr, step, tile_counter, block_counts, grid_out, adapt, img_words, st);
-    return launch_pcn_flow_fused<float>(ctx, n, ll, lp, lq, pd, f, rho_ptr, step, tile_counter, block_counts, grid_out, adapt, img_words, st);
+        return launch_pcn_flow_fused<double>(ctx, n, ll, lp, lq, pd, f, rho_ptr, step, tile_counter, block_counts, grid_out, adapt, img_words,
+                                             no_density, st);
+    return launch_pcn_flow_fused<float>(ctx, n, ll, lp, lq, pd, f, rho_ptr, step, tile_counter, block_counts, grid_out, adapt, img_words,
+                                        no_density, st);
+}
+
+// ---- beta = 1: the steps without the density, one refresh of log q behind them ---------------------------------------------------
+// Whether a call at beta = 1 exactly can run that way: the matrix-core in-place build, an image to run from (not ASMC_FUSED_STAGE=inline),
+// split-fp16 flow math and a flow the refresh is compiled for - the fused step's own widths and kinds.  ASMC_FLOW_BETA1=full (read
+// per call) keeps the full step, so that one process can compare the two.
+bool asmc_pcn_flow_fused_beta1_ok(const asmc_coupling* f, int img_words) {
+#if FUSED_MVMFMA && FUSED_INPLACE
+    const char* mode = getenv("ASMC_FLOW_BETA1");
+    if (mode && !strcmp(mode, "full")) return false;
+    if (img_words <= 0 || !asmc_flow_math_split()) return false;
+#ifdef FUSED_ONLY_HEADLINE
+    return f->kind == ASMC_FLOW_COUPLING && f->hidden == 64;
+#else
+    if (f->kind == ASMC_FLOW_MAF) return f->hidden == 32 || f->hidden == 64;
+    return f->kind == ASMC_FLOW_COUPLING && (f->hidden == 32 || f->hidden == 64 || f->hidden == 128);
+#endif
+#else
+    (void)f, (void)img_words;
+    return false;
+#endif
+}
+
+#if FUSED_MVMFMA && FUSED_INPLACE
+template <typename T>
+static int launch_fused_lq_refresh(asmc_ctx* ctx, int64_t n, double* lq, const PcnDev& pd, const asmc_coupling* f, const double* rho_ptr,
+                                   unsigned long long* nonfinite, hipStream_t st) {
+    const PcnScalars ps = fused_scalars(pd);
+    const float ladj0 = (float)(-f->log_scale_sum);
+    const float base_const = (float)(-0.5 * f->dims * 1.8378770664093453);
+    const int64_t n_tiles = (n + 63) / 64;
+    const int grid = (int)(n_tiles < (int64_t)ctx->num_cu * (FUSED_THREADS / 64) ? (n_tiles + FUSED_THREADS / 64 - 1) / (FUSED_THREADS / 64) : ctx->num_cu);
+    const int words = fused_table_word0(f) + (int)(FUSED_TL_DOUBLES * sizeof(double) / 16);  // weights and pCN tables: no noise, no Box-Muller part
+    const size_t lds = (size_t)words * 16;
+#define ASMC_FUSED_LQ_CASE(WW, KD)                                                                                               \
+    if (f->hidden == WW && f->kind == KD) {                                                                                      \
+        auto kern = k_pcn_flow_fused_lq<T, WW, KD>;                                                                              \
+        static size_t attr_lds_dev[ASMC_MAX_DEVICES] = {0}; size_t& attr_lds = attr_lds_dev[asmc_dev_slot(ctx)];                 \
+        if (lds > 64 * 1024 && lds > attr_lds) {                                                                                 \
+            ASMC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            attr_lds = lds;                                                                                                      \
+        }                                                                                                                        \
+        ASMC_LAUNCH(ctx, st, "k_fused_lq_refresh", kern, dim3(grid), dim3(FUSED_THREADS), lds, st, n, lq, ps, rho_ptr, (int)f->n_layers, ladj0, \
+                    base_const, nonfinite, KD == ASMC_FLOW_MAF ? (int)f->affine : 0, reinterpret_cast<const fused_u4*>(ctx->d_fimg), words, \
+                    ctx->d_flags + scratch_flags_moved_off(n));                                                                  \
+        ASMC_LAUNCH_CHECK();                                                                                                     \
+        return ASMC_OK;                                                                                                          \
+    }
+    ASMC_FUSED_LQ_CASE(64, ASMC_FLOW_COUPLING)
+#ifndef FUSED_ONLY_HEADLINE
+    ASMC_FUSED_LQ_CASE(32, ASMC_FLOW_COUPLING)
+    ASMC_FUSED_LQ_CASE(128, ASMC_FLOW_COUPLING)
+    ASMC_FUSED_LQ_CASE(64, ASMC_FLOW_MAF)
+    ASMC_FUSED_LQ_CASE(32, ASMC_FLOW_MAF)
+#endif
+#undef ASMC_FUSED_LQ_CASE
+    asmc_set_error("fused log q refresh: unsupported flow (kind %d, hidden width %d)", (int)f->kind, (int)f->hidden);
+    return ASMC_ERR_UNSUPPORTED;
+}
+#endif
+
+// log q of the particles the call's steps moved (the marks behind ctx->d_flags' parities: asmc_scratch.h), from the whitened state and the call's image
+int asmc_pcn_flow_fused_refresh(asmc_ctx* ctx, int64_t n, int x_dtype, double* lq, const PcnDev& pd, const asmc_coupling* f,
+                                const double* rho_ptr, unsigned long long* nonfinite, hipStream_t st) {
+#if FUSED_MVMFMA && FUSED_INPLACE
+    if (x_dtype == ASMC_F64) return launch_fused_lq_refresh<double>(ctx, n, lq, pd, f, rho_ptr, nonfinite, st);
+    return launch_fused_lq_refresh<float>(ctx, n, lq, pd, f, rho_ptr, nonfinite, st);
+#else
+    asmc_set_error("fused log q refresh: not in this build");
+    return ASMC_ERR_UNSUPPORTED;
+#endif
 }

@@ -73,6 +73,24 @@ static inline long long* scratch_count_total(const asmc_ctx* ctx) { return ctx->
 constexpr bool scratch_tiles_fit(int64_t t) { return 4 * t <= (int64_t)scratch_tiles_len(t) && 8 * t + 1 <= (int64_t)scratch_tiles_i_len(t); }
 static_assert(scratch_tiles_fit(1) && scratch_tiles_fit(1 << 20), "four / eight entries per tile and the total lie inside the tile arrays");
 
+// ---- ctx->d_flags: bytes right behind the fused step's counters, inside ctx->d_tilectr's allocation; all TRANSIENT ----------------
+// Three users, each inside one exported call (a context carries one mutation at a time):
+//   accept flags   [0, n)             asmc_pcn.hip: the split path's accept decision (pcn_accept_flags_launch -> launch_copy_flagged)
+//   tile parities  [0, ceil(n / 64))  a fused flow mutation: which half of the state holds a tile.  Zeroed by the call; the in-place
+//                                     build (FUSED_INPLACE 1) never flips one, but the call's un-whitening launch READS them
+//                                     (k_pcn_reg, PCN_UNWHITEN_X) - so nothing else of that call may live in these bytes
+//   moved marks    [P, P + n)         P = scratch_flags_moved_off(n), behind the parities.  A fused flow mutation at beta = 1: 1 where
+//                                     a step without the density accepted; zeroed by the call's fill, written by its steps, read by
+//                                     its one log q refresh, dead after it
+// The call's fill covers the counters in front and these bytes in one piece, rounded up to 16 bytes (a ragged memset is two fill kernels).
+constexpr size_t SCRATCH_FLAGS_SLACK = 64;
+constexpr size_t scratch_flags_len(int64_t n_max) { return (size_t)n_max + (size_t)n_max / 64 + SCRATCH_FLAGS_SLACK; }
+constexpr size_t scratch_flags_fill(int64_t entries) { return ((size_t)entries + 15) / 16 * 16; }
+constexpr size_t scratch_flags_moved_off(int64_t n) { return scratch_flags_fill((n + 63) / 64); }
+constexpr bool scratch_flags_fit(int64_t n) { return scratch_flags_moved_off(n) + scratch_flags_fill(n) <= scratch_flags_len(n); }
+static_assert(scratch_flags_fit(1) && scratch_flags_fit(63) && scratch_flags_fit(193) && scratch_flags_fit(1 << 20) && scratch_flags_fit((1 << 20) + 1),
+              "parities and moved marks, each rounded to 16 bytes, stay inside the allocation");
+
 // ---- the checks ------------------------------------------------------------------------------------------------------------
 struct ScratchRegion {
     int buf, off, len, held;  // buf: 0 = d_small, 1 = h_pinned

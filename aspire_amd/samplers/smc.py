@@ -924,8 +924,13 @@ class HipSMC(SMCSampler):
                 done += chunk
                 n_bad = e.pcn_flow_nonfinite() if hasattr(e, "pcn_flow_nonfinite") else 0
                 if n_bad > 0:
-                    logger.warning(f"{n_bad} proposals had a non-finite flow density and were rejected (a badly scaled flow "
-                                   "overflows the fp16 operand pairs of the flow kernel; ASMC_FLOW_MATH=f32 uses fp32 MFMAs)")
+                    # beta = 1: the steps do not look at the flow density (the tempered target has no log q term), so such a
+                    # proposal was accepted or rejected on the targets alone and the refresh behind the steps found the NaN
+                    what = ("particles moved at beta = 1 carry a non-finite flow density (the accept test has no log q term there; "
+                            "the check of the carried log q raises on them)" if beta == 1.0
+                            else "proposals had a non-finite flow density and were rejected")
+                    logger.warning(f"{n_bad} {what} (a badly scaled flow overflows the fp16 operand pairs of the flow kernel; "
+                                   "ASMC_FLOW_MATH=f32 uses fp32 MFMAs)")
         else:
             for t in range(n_steps):
                 n_acc, _, _ = e.pcn_mutate_flow(x, ll, lp, lq, beta, mu, L, Linv, t_ll, t_lp, dev_flow, seed, gid0,

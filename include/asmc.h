@@ -697,7 +697,18 @@ int asmc_maf_pack(int dims, int n_transforms, int hidden, const float* const* we
  * of a built-in mixture (params->log_q is ignored): per step propose -> log q(x') on the MFMA ->
  * built-in log prior / log likelihood -> accept -> device-side adaptation, all enqueued without host
  * round trips (smc/minipcn.py:97-114 + smc/base.py:507-519 with a flow proposal, BASELINE config 3).
- * work_dev: caller-owned scratch of asmc_pcn_flow_work_bytes(n, d, x_dtype) bytes. */
+ * work_dev: caller-owned scratch of asmc_pcn_flow_work_bytes(n, d, x_dtype) bytes.
+ * params->beta == 1.0 exactly (the last temperature of every SMC run), one-kernel step at d <= 32 with split-fp16 flow math:
+ * the tempered target is 0 * lq + (ll + lp), no accept decision reads log q, so the steps run WITHOUT the flow and one pass
+ * behind the last step stores log q of the particles that moved (profile labels: k_pcn_flow_fused as ever, then one
+ * k_fused_lq_refresh).  Results are those of the full step bit for bit - x, ll, lp, lq, accept counts, step sizes; a particle
+ * that never moved keeps the lq it came in with - in every call in which no proposal has a non-finite flow density.  (The one
+ * known exception: 0 * lq is -0 for a negative lq, the stored placeholder is +0, which differs only where beta (ll + lp) is
+ * itself -0.)  A proposal whose density overflows the fp16 operand range is rejected and counted at every other beta; at
+ * beta = 1 it is accepted or rejected on the targets alone, the refresh finds its log q non-finite, counts it
+ * (asmc_pcn_flow_nonfinite) and the carried lq is NaN (asmc_pcn_lq_nan).  Any other beta, however close to 1, and
+ * ASMC_FLOW_BETA1=full in the environment (read per call) take the full step.  The 32 < d <= 128 step and the split
+ * propose / flow / accept loops evaluate the flow at every beta. */
 int64_t asmc_pcn_flow_work_bytes(int64_t n, int d, int x_dtype);
 int asmc_pcn_mutate_flow(asmc_ctx* ctx, int64_t n, void* x_dev, double* ll_dev, double* lp_dev,
                          double* lq_dev, const asmc_pcn_params* params, const asmc_coupling* flow,
@@ -717,7 +728,8 @@ int asmc_pcn_mutate_flow_enqueue(asmc_ctx* ctx, int64_t n, void* x_dev, double* 
                                  int64_t work_bytes, int n_steps, uint32_t step0, double rho, asmc_stream stream);
 int asmc_pcn_mutate_flow_result(asmc_ctx* ctx, int n_steps, double* rho_out_host, int64_t* n_accept_host,
                                 double* rho_hist_host, asmc_stream stream);
-/* Proposals of the last asmc_pcn_mutate_flow whose flow density was not finite (they were rejected).  The flow's fp32 layers
+/* Proposals of the last asmc_pcn_mutate_flow whose flow density was not finite (they were rejected; at beta = 1: particles the
+ * call moved whose refreshed log q is not finite - see asmc_pcn_mutate_flow).  The flow's fp32 layers
  * run as split-fp16 MFMA products (operands |.| < 65504): a badly scaled flow shows up here; ASMC_FLOW_MATH=f32 selects the
  * fp32 MFMA chain.  Counted by the one-kernel step only. */
 int64_t asmc_pcn_flow_nonfinite(asmc_ctx* ctx);
