@@ -26,7 +26,7 @@ COUNT_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 ASMC_BIS_REC = 40
 ASMC_SELECT_THREADS = 262144
 ASMC_STUDENT_MAX_ROWS = 16384
-ASMC_ABI_VERSION = 29
+ASMC_ABI_VERSION = 30
 ASMC_FLOW_COUPLING, ASMC_FLOW_MAF = 0, 1  # asmc_coupling.kind
 ASMC_MAX_COUNT_CELLS = 64  # asmc_pcn_set_count_cells
 ASMC_CDF_REC = 9
@@ -293,6 +293,11 @@ SIGNATURES = {
     "asmc_chain_clear": (_i, [_vp]),
     "asmc_pt_swap": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp]),
     "asmc_pt_evidence": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "asmc_pt_steps_supported": (_i, [_i, _i, _vp]),
+    "asmc_pt_pack": (_i, [_vp, _i, _i64, POINTER(AsmcPcnParams), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), _pd, _vp]),
+    "asmc_pt_steps": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, POINTER(AsmcPcnParams), _vp, _vp, _vp, _i, _u32, POINTER(AsmcChainTarget),
+                           _i64, _vp]),
+    "asmc_pt_ladder_adapt": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _d, _d, _vp]),
 }
 
 _lib = None

@@ -179,6 +179,12 @@ struct asmc_ctx {
     int64_t chain_lq_n;
     void* d_chain_rows;            // [chain_rows_bytes] n rows of the padded width: where a zero-padded call un-whitens for the recorder
     size_t chain_rows_bytes;
+    // rung-batched tempered steps (asmc_pt_steps.hip): T packed table blocks | nu [T] | the step kernel's block counts; grown by
+    // asmc_pt_pack, which also notes what it packed
+    double* d_pt;
+    size_t pt_bytes;
+    int pt_T, pt_d, pt_tp, pt_grid, pt_c[3];
+    int64_t pt_W;
 };
 #include "asmc_scratch.h"
 

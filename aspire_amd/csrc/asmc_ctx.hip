@@ -257,6 +257,7 @@ int asmc_ctx_destroy(asmc_ctx* c) {
     if (c->d_xpad) (void)hipFree(c->d_xpad);
     if (c->d_chain_lq) (void)hipFree(c->d_chain_lq);
     if (c->d_chain_rows) (void)hipFree(c->d_chain_rows);
+    if (c->d_pt) (void)hipFree(c->d_pt);
     (void)hipFree(c->d_counts);
     (void)hipFree(c->d_rho);
     (void)hipFree(c->d_stretch);

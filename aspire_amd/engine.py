@@ -1303,6 +1303,56 @@ class HipEngine:
                                         self._stream), "asmc_pt_evidence")
         return out.cpu().numpy()
 
+    # ---- rung-batched steps and the adaptive ladder (include/asmc.h asmc_pt_steps_supported / _pack / _steps / _ladder_adapt) -------------
+    def pt_steps_supported(self, x) -> bool:
+        """Whether the rung-batched step kernels take the state x [T W, d]: d in {4, 8, 16, 32}, 16-byte aligned rows."""
+        return bool(self.lib.asmc_pt_steps_supported(int(x.shape[1]), self._xdt(x), _dptr(x)))
+
+    def pt_pack(self, x, n_temps: int, refs, t_ll: DeviceMixture, t_lp: DeviceMixture, t_lq: DeviceMixture):
+        """Packs the rungs' tables for `pt_steps` on the state x [T W, d]: refs[r] = (mu, L, Linv, nu) of rung r (device tensors;
+        nu > 0: Student-t reference, else Gaussian) and the three built-in densities.  May allocate.  Returns the handle `pt_steps`
+        takes; it keeps the tensors alive."""
+        n, d = x.shape
+        assert n % n_temps == 0 and len(refs) == n_temps
+        arr = ctypes.c_void_p * n_temps
+        for mu, L, Linv, _ in refs:
+            assert all(t.dtype == torch.float64 and t.is_contiguous() for t in (mu, L, Linv)) and mu.numel() == d and L.numel() == d * d
+        nu = np.ascontiguousarray([float(r[3]) for r in refs], dtype=np.float64)
+        prm = AsmcPcnParams(d, self._xdt(x), 1.0, None, None, None, t_ll.c_struct(), t_lp.c_struct(), t_lq.c_struct(), 0, 0, 0.234, 1, 0, 0.0)
+        check(self.lib.asmc_pt_pack(self._ctx, n_temps, n // n_temps, ctypes.byref(prm), arr(*[r[0].data_ptr() for r in refs]),
+                                    arr(*[r[1].data_ptr() for r in refs]), arr(*[r[2].data_ptr() for r in refs]), _f64p(nu), self._stream),
+              "asmc_pt_pack")
+        return {"n_temps": n_temps, "n_walkers": n // n_temps, "prm": prm, "keep": (refs, t_ll, t_lp, t_lq)}
+
+    def pt_steps(self, pack, x, ll, lp, lq, betas, rho, accept, seed: int, n_steps: int, step0: int = 0, target_accept: float = 0.234,
+                 adapt: bool = True, chain: DeviceChain | None = None, n_slots: int = 0, slot0: int = 0):
+        """n_steps Markov steps of every rung from Philox step `step0`, one step kernel per step whatever the number of rungs.
+        betas, rho [T] (fp64) and accept [T] (int64, cumulative) are device tensors; `chain`: rows [T n_slots, W, d] read as
+        [T, n_slots, W, d], slot slot0 + t of every rung <- the state after step t.  Only enqueues."""
+        T, W = pack["n_temps"], pack["n_walkers"]
+        assert x.is_contiguous() and tuple(x.shape) == (T * W, pack["prm"].d) and self._xdt(x) == pack["prm"].x_dtype
+        self._chk3(ll, lp, lq)
+        for v, dt in ((betas, torch.float64), (rho, torch.float64), (accept, torch.int64)):
+            assert v.dtype == dt and v.is_contiguous() and v.numel() == T
+        prm = pack["prm"]
+        prm.seed, prm.target_accept, prm.adapt = int(seed), float(target_accept), int(bool(adapt))
+        c = None
+        if chain is not None:
+            assert chain.x.is_contiguous() and chain.x.dtype == x.dtype and chain.x.numel() == T * n_slots * W * prm.d
+            c = AsmcChainTarget(chain.x.data_ptr(), chain.ll.data_ptr(), chain.lp.data_ptr(), int(n_slots), W, prm.d, 0, prm.d, prm.x_dtype, 1, 0)
+        check(self.lib.asmc_pt_steps(self._ctx, T, W, _dptr(x), _dptr(ll), _dptr(lp), _dptr(lq), ctypes.byref(prm), _dptr(betas), _dptr(rho),
+                                     _dptr(accept), int(n_steps), int(step0), ctypes.byref(c) if c is not None else None, int(slot0),
+                                     self._stream), "asmc_pt_steps")
+
+    def pt_ladder_adapt(self, n_walkers: int, counts, snap, betas, history, update: int, lag: float, time: float):
+        """Ladder update number `update` >= 1 (include/asmc.h asmc_pt_ladder_adapt) from the exchange counts [T - 1] (int64) since
+        `snap`; betas [T] moves between its fixed ends, row `update` of history [., T] <- the new ladder.  Only enqueues."""
+        T = int(betas.numel())
+        assert counts.dtype == torch.int64 and snap.dtype == torch.int64 and counts.numel() >= T - 1 and snap.numel() >= T - 1
+        assert betas.dtype == torch.float64 and history.dtype == torch.float64 and history.is_contiguous() and history.numel() >= (update + 1) * T
+        check(self.lib.asmc_pt_ladder_adapt(self._ctx, T, int(n_walkers), _dptr(counts), _dptr(snap), _dptr(betas), _dptr(history), int(update),
+                                            float(lag), float(time), self._stream), "asmc_pt_ladder_adapt")
+
     # ---- random-walk MH and HMC of the "blackjax_smc" sampler (include/asmc.h asmc_rw_* / asmc_mh_* / asmc_hmc_*) ---------------
     def rw_propose(self, x, sigma, seed: int, gid0: int, step: int, t: int):
         """y = x + sigma xi in x's dtype.  `sigma`: a float (standard deviation), a device [d] tensor (per-coordinate standard

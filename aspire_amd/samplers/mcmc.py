@@ -280,6 +280,7 @@ class HipEmcee(ChainSampler):
 
 
 PT_MAX_RUNGS = 64  # include/asmc.h ASMC_PT_MAX_RUNGS
+LADDER_LAG, LADDER_TIME = 10.0, 1.0  # the adaptive ladder's t0 and nu (the sweep behind them)
 
 
 def default_ladder(n_temps: int, beta_min: float) -> np.ndarray:
@@ -306,14 +307,30 @@ class HipPTMiniPCN(ChainSampler):
     every `swap_every` steps one `asmc_pt_swap` with round index t / swap_every - 1 (0: never).  chain[r, t] is rung r's state
     after the move of step t and before the exchange that may follow it.  `n_samples` only gives the default number of walkers per
     rung - the result is the whole processed chain, which cannot be sliced -, and `n_temps` / `beta_min` are read only when `betas`
-    is not given."""
+    is not given.
+
+    `rung_launch` changes the launches, not the results.  "per_rung" (the default): every rung's steps are an
+    `asmc_pcn_mutate` call of its own, which synchronises.  "batched": one `asmc_pt_steps` call steps all rungs, with the rungs' betas,
+    references, step sizes and accept counts in device tables; nothing is read back before the run ends.  Its scope is built-in
+    mixture densities under the identity transform at d in {4, 8, 16, 32} with the default noise - anything else raises
+    NotImplementedError, there is no fallback.  (The batched steps run on x itself; a per-rung call of 4 or more steps runs on
+    the whitened state, which agrees with it to rounding only: the two are bit-identical where every segment has fewer than 4
+    steps, e.g. `swap_every` in 1 .. 3.)
+
+    `adapt_ladder=True` (batched only; Vousden, Farr & Mandel 2016): after every odd exchange round k with (k + 1) swap_every <=
+    burnin - every pair has then been tried once since the last update - `asmc_pt_ladder_adapt` moves the interior betas towards
+    equal swap acceptance, with gain kappa = ladder_lag / (ladder_time (m - 1 + ladder_lag)) at update m.  Afterwards the ladder is
+    frozen: `betas` and the returned container carry the final ladder, `ladder_history` [n_updates + 1, T] every ladder, and
+    `evidence` is computed from the steps at or after `burnin` alone - earlier steps were drawn on other ladders.  The checkpointed
+    full chain contains those earlier steps.  `swap_acceptance_kept` is the pairs' acceptance over the exchange rounds behind
+    `burnin` (batched runs, adaptive or not; None otherwise: the per-rung path launches nothing it did not launch before)."""
 
     _fit_reference = HipSMC._fit_reference
     _fit_reference_gaussian = HipSMC._fit_reference_gaussian
     _upload_reference = HipSMC._upload_reference
     _check_reference_fit = HipSMC._check_reference_fit
 
-    rung_acceptance = rung_step_size = swap_acceptance = evidence = None
+    rung_acceptance = rung_step_size = swap_acceptance = swap_acceptance_kept = evidence = betas = ladder_history = None
 
     def log_likelihood_wrapper(self, z):
         """mcmc.py:354-360: log L at x = T^-1(z), for array input."""
@@ -332,10 +349,16 @@ class HipPTMiniPCN(ChainSampler):
     def sample(self, n_samples: int | None = None, n_walkers: int | None = None, n_temps: int = 8, betas=None, beta_min: float = 1e-3,
                n_steps: int = 100, swap_every: int = 1, burnin: int = 0, thin: int = 1, step_fn: str = "tpcn",
                target_acceptance_rate: float = 0.234, refit_every: int | None = None, rng=None, checkpoint_callback=None,
-               checkpoint_every: int | None = None, checkpoint_file_path: str | None = None):
+               checkpoint_every: int | None = None, checkpoint_file_path: str | None = None, rung_launch: str = "per_rung",
+               adapt_ladder: bool = False, ladder_lag: float = LADDER_LAG, ladder_time: float = LADDER_TIME, noise: str = "f64"):
         self._single_rank()
         if step_fn not in ("pcn", "tpcn"):
             raise NotImplementedError(f"step_fn={step_fn!r} is not implemented by the HIP step kernels; use step_fn='tpcn' or 'pcn'")
+        if rung_launch not in ("per_rung", "batched"):
+            raise ValueError(f"rung_launch must be 'per_rung' or 'batched', got {rung_launch!r}")
+        if noise not in ("f64", "f32"):
+            raise ValueError(f"noise must be 'f64' or 'f32', got {noise!r}")
+        batched = rung_launch == "batched"
         e = self.engine
         rng = rng or self.rng or np.random.default_rng()
         if not (n_walkers or n_samples):
@@ -354,12 +377,38 @@ class HipPTMiniPCN(ChainSampler):
             raise ValueError("n_steps must be at least 1")
         if swap_every < 0 or (refit_every is not None and int(refit_every) < 1):
             raise ValueError("swap_every must be non-negative and refit_every positive")
+        burnin = int(burnin)
+        if adapt_ladder:
+            if not batched:
+                raise ValueError("adapt_ladder needs rung_launch='batched': the ladder moves on the device")
+            if swap_every < 1:
+                raise ValueError("adapt_ladder needs swap_every >= 1: the update reads the exchange's acceptance")
+            if n_t < 3:
+                raise ValueError("adapt_ladder needs at least 3 rungs: the two ends of the ladder are fixed")
+            if ladder[-1] != 0.0:
+                raise ValueError("adapt_ladder needs a ladder that ends at 0: the hot end is fixed at infinite temperature")
+            if burnin < 2 * swap_every:
+                raise ValueError("adapt_ladder needs burnin >= 2 swap_every: the ladder moves during burn-in only, after two rounds")
+            if burnin >= n_steps:
+                raise ValueError("adapt_ladder needs burnin < n_steps: the evidence comes from the steps behind burnin, on the final ladder")
+            if not (float(ladder_lag) > 0.0 and float(ladder_time) > 0.0):
+                raise ValueError("ladder_lag and ladder_time must be positive")
         self._check_chain_memory(n_t * n_steps, W)
         if hasattr(e, "ensure_capacity"):
             e.ensure_capacity(n_t * W, self.dims)
         self.history = SMCHistory()
         self.sampler_kwargs = {"step_fn": step_fn}
         _, z, logj, ll, lp, T = self._start(n_t * W)
+        builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
+        if batched:
+            why = ("the densities are callables" if not builtin else "the chain runs in a preconditioned space (a transform)" if T is not None
+                   else f"noise={noise!r}" if noise != "f64"
+                   else f"d={self.dims} is not one of 4, 8, 16, 32 with 16-byte aligned rows" if not e.pt_steps_supported(z) else None)
+            if why:
+                raise NotImplementedError(f"rung_launch='batched' steps built-in mixture densities under the identity transform at d in "
+                                          f"{{4, 8, 16, 32}} with the default noise: {why}; use rung_launch='per_rung'")
+        elif noise != "f64" and not (T is None and builtin):
+            raise NotImplementedError("noise='f32' is implemented for built-in densities under the identity transform only")
         rows = [slice(r * W, (r + 1) * W) for r in range(n_t)]
         states = [{"rho": min(2.38 / math.sqrt(self.dims), 0.99), "step": 0, "nu": None} for _ in range(n_t)]
         refs = [None] * n_t
@@ -379,40 +428,91 @@ class HipPTMiniPCN(ChainSampler):
         lq = lp.clone()  # the proposal-density slot carries the prior's value: (1 - beta) lq + beta (ll + lp) = lp + beta ll
         betas_dev = e.asarray(ladder)
         counts = torch.zeros(max(n_t - 1, 1), dtype=torch.int64, device=betas_dev.device)
-        builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
         stepper = self._segment_fused if T is None and builtin else self._segment_generic
+        self._noise = noise
         run = (z, logj, ll, lp, lq, T, rows, ladder, states, refs, seed, float(target_acceptance_rate), chains)
         refit_every = None if refit_every is None else int(refit_every)
         accepted, done, n_rounds = np.zeros(n_t), 0, 0
+        kept0, rounds0 = None, 0  # (batched) the exchange counts when the kept steps begin
+        if batched:
+            if burnin <= 0:
+                kept0 = counts.clone()
+            # what the per-rung path keeps on the host, as device tables; the ladder's history (row 0: the given ladder)
+            rho_dev = e.asarray(np.array([st["rho"] for st in states]))
+            accept_dev, snap = torch.zeros(n_t, dtype=torch.int64, device=betas_dev.device), torch.zeros_like(counts)
+            n_updates = (burnin // swap_every) // 2 if adapt_ladder else 0
+            history = torch.zeros((n_updates + 1, n_t), dtype=torch.float64, device=betas_dev.device)
+            history[0].copy_(betas_dev)
+            t_ll, t_lp = self._log_likelihood.device_mixture(e), self._log_prior.device_mixture(e)
+            pack, updates = None, 0
+            self.last_mutation_path = ("built-in densities: all rungs in one device-side step loop (asmc_pt_steps) on device tables of "
+                                       "beta_r, reference, step size and counts, recorded by its own launch; exchange by asmc_pt_swap"
+                                       + ("; ladder adapted by asmc_pt_ladder_adapt" if adapt_ladder else ""))
         try:
             while done < n_steps:
                 if done and refit_every and done % refit_every == 0 and done < burnin:
                     for r in range(n_t):
                         refit(r)
+                    pack = None
+                if batched and pack is None:
+                    pack = e.pt_pack(z, n_t, refs, t_ll, t_lp, t_lp)
                 stops = [n_steps, done + MAX_CHUNK]
                 if swap_every:
                     stops.append((done // swap_every + 1) * swap_every)
                 if refit_every and done < burnin:
                     stops.append((done // refit_every + 1) * refit_every)
                 chunk = min(stops) - done
-                accepted += stepper(run, done, chunk)
+                if batched:  # (the adaptation index restarts with the call, as it does per rung)
+                    e.pt_steps(pack, z, ll, lp, lq, betas_dev, rho_dev, accept_dev, seed, chunk, done, float(target_acceptance_rate), True,
+                               chain=chain, n_slots=n_steps, slot0=done)
+                    self.n_likelihood_evaluations += chunk * z.shape[0]
+                else:
+                    accepted += stepper(run, done, chunk)
                 done += chunk
                 if swap_every and n_t > 1 and done % swap_every == 0:
-                    e.pt_swap(z, ll, lp, betas_dev, seed, done // swap_every - 1, counts, c0=lq, c1=logj)
+                    k = done // swap_every - 1
+                    e.pt_swap(z, ll, lp, betas_dev, seed, k, counts, c0=lq, c1=logj)
                     n_rounds += 1
+                    if adapt_ladder and k % 2 == 1 and done <= burnin:
+                        e.pt_ladder_adapt(W, counts, snap, betas_dev, history, (k + 1) // 2, float(ladder_lag), float(ladder_time))
+                        updates += 1
+                if batched and kept0 is None and done >= burnin:
+                    kept0, rounds0 = counts.clone(), n_rounds
         finally:
             e.chain_clear()
+        if batched:  # the one read of the run's tables
+            accepted = to_numpy(accept_dev).astype(np.float64)
+            self.rung_step_size = np.asarray(to_numpy(rho_dev), dtype=np.float64).copy()
+            self.ladder_history = np.asarray(to_numpy(history), dtype=np.float64)[:updates + 1].copy()
+            ladder = self.ladder_history[-1].copy()
+        else:
+            self.rung_step_size = np.array([st["rho"] for st in states])
+            self.ladder_history = ladder[None, :].copy()
+        self.betas = ladder
         self.rung_acceptance = accepted / (n_steps * W)
-        self.rung_step_size = np.array([st["rho"] for st in states])
-        tries = np.array([len(range(r % 2, n_rounds, 2)) for r in range(n_t - 1)], dtype=np.float64) * W
+        pair_tries = lambda k0: np.array([len(range(k0 + (r - k0) % 2, n_rounds, 2)) for r in range(n_t - 1)], dtype=np.float64) * W  # noqa: E731
+        tries = pair_tries(0)
         got = to_numpy(counts)[:n_t - 1].astype(np.float64)  # the one read of the device counts
         self.swap_acceptance = np.divide(got, tries, out=np.zeros(n_t - 1), where=tries > 0)
+        if batched:
+            if kept0 is None:
+                kept0, rounds0 = counts, n_rounds
+            tries = pair_tries(rounds0)
+            self.swap_acceptance_kept = np.divide(got - to_numpy(kept0)[:n_t - 1].astype(np.float64), tries, out=np.zeros(n_t - 1),
+                                                  where=tries > 0)
+        else:
+            self.swap_acceptance_kept = None
         self.history.mcmc_acceptance.append(float(self.rung_acceptance[0]))
         self.history.mcmc_step_size.append(float(self.rung_step_size[0]))
         full = PTMCMCSamples.from_chain(chain=x4, betas=ladder, log_likelihood=ll3, log_prior=lp3, parameters=self.parameters, xp=torch,
                                         dtype=self.dtype, thin=1, burn_in=0, engine=e)
-        self.evidence = {"thermodynamic_integration": full.log_evidence_thermodynamic_integration(),
-                         "stepping_stone": full.log_evidence_stepping_stone() if ladder[-1] == 0.0 else None}
+        if adapt_ladder:  # only the steps on the final ladder
+            kept = full.post_process(burn_in=burnin)
+            self.evidence = {"thermodynamic_integration": kept.log_evidence_thermodynamic_integration(burn_in_fraction=None),
+                             "stepping_stone": kept.log_evidence_stepping_stone(burn_in_fraction=None)}
+        else:
+            self.evidence = {"thermodynamic_integration": full.log_evidence_thermodynamic_integration(),
+                             "stepping_stone": full.log_evidence_stepping_stone() if ladder[-1] == 0.0 else None}
         full = self._out(full)
         self.checkpoint_mcmc_chain(samples=full, iteration=n_steps, checkpoint_callback=checkpoint_callback,
                                    checkpoint_every=checkpoint_every, checkpoint_file_path=checkpoint_file_path)
@@ -431,7 +531,7 @@ class HipPTMiniPCN(ChainSampler):
             mu, L, Linv, nu = refs[r]
             e.chain_set(chains[r], t0, 1)
             n_acc, _, states[r]["rho"] = e.pcn_mutate(z[sl], ll[sl], lp[sl], lq[sl], float(ladder[r]), mu, L, Linv, t_ll, t_lp, t_lp, seed,
-                                                      r * z[sl].shape[0], states[r]["rho"], chunk, t0, target, 1, "f64", nu)
+                                                      r * z[sl].shape[0], states[r]["rho"], chunk, t0, target, 1, self._noise, nu)
             acc[r] = float(np.sum(n_acc))
         self.n_likelihood_evaluations += chunk * z.shape[0]
         return acc

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 29
+#define ASMC_ABI_VERSION 30
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -1032,6 +1032,47 @@ int asmc_pt_swap(asmc_ctx* ctx, int n_temps, int64_t n_walkers, int d, int x_dty
                  asmc_stream stream);
 int asmc_pt_evidence(asmc_ctx* ctx, int n_temps, int64_t stride, int64_t offset, int64_t n, const double* ll_dev,
                      const double* coef_dev, double* out_dev, asmc_stream stream);
+
+/* ---- rung-batched steps and the adaptive ladder of the "pt_minipcn" sampler (ABI 30) -----------------
+ * The state of asmc_pt_swap, stepped by ONE kernel per Markov step whatever the number of rungs: grid (tiles of W, T), block
+ * (., r) runs the x-state step of asmc_pcn_mutate (the kernel body of a call of fewer than 4 steps) on rung r's rows with
+ * beta = betas_dev[r], the reference of rung r, the step size rho_dev[r] and the noise / accept streams of gid = r W + w.
+ * Scope: built-in mixture densities, d in {4, 8, 16, 32} with 16-byte aligned x_dev (asmc_pt_steps_supported), both storage types,
+ * pCN and tpCN, the default fp64 noise, adapt 0 or 1, one rank.  Anything else: ASMC_ERR_UNSUPPORTED with the reason.
+ *
+ * asmc_pt_steps_supported: 1 when (d, x_dtype, x_dev) is inside the scope, else 0.
+ *
+ * asmc_pt_pack: gathers the T rungs' tables into context scratch (T blocks of the register kernels' packed layout: L, Linv, mu
+ * of rung r from mu_dev[r] / L_dev[r] / Linv_dev[r] - HOST arrays of T device pointers - and the three mixtures of `params`) and
+ * keeps nu_host[r] beside them: >= 1, rung r has a Student-t reference (tpCN); <= 0, or nu_host NULL, a Gaussian one (pCN) - a
+ * tpCN fit may give single rungs the latter.  Of `params` it reads d, x_dtype and the mixtures.  The only entry point of the three that may allocate (the scratch grows on
+ * demand, synchronising the device when it does); the tables travel as kernel arguments, nothing is staged.
+ *
+ * asmc_pt_steps: n_steps Markov steps, step t with the Philox step index step0 + t, on the tables of the last asmc_pt_pack (T,
+ * W and d must be the packed ones).  Per step: the scale variates of every Student-t rung in one launch where the batch of
+ * ASMC_GAMMA_BATCH steps does not hold them (shape (d + nu_r) / 2, the values of asmc_pcn_mutate at gid0 = r W), the step
+ * kernel (both of its forms, over the same grid, where the rungs' references are of both kinds), one closing launch - block r sums rung r's block counts, accept_dev[r] += the sum, and with params->adapt
+ * rho_dev[r] <- the step-size update of asmc_pcn_mutate at index t, the step's index WITHIN the call - and, chain != NULL, one
+ * recording launch: rung r's rows and carried ll / lp -> slot slot0 + t of rung r in a chain [T, chain->n_slots, W, d]
+ * (chain->n = W, pitch = d; rung r's slot s starts (r n_slots + s) W rows into x_dev / ll_dev / lp_dev; 16-byte vectors where
+ * rows and both pointers allow, element-wise otherwise).  betas_dev, rho_dev [T] (fp64) and accept_dev [T] (int64, cumulative)
+ * are the caller's device arrays.  Only enqueues: no synchronisation, no allocation, no read-back; the launches per step do not
+ * depend on T.  The context's single-mutation cells (step size, per-step counts) are not touched; the variates' batch is left
+ * invalidated, so a later asmc_pcn_mutate draws its own.
+ *
+ * asmc_pt_ladder_adapt: update number `update` = m >= 1 of the ladder (Vousden, Farr & Mandel 2016), one small block, fp64.
+ *     A_r = (counts_dev[r] - snap_dev[r]) / W, r = 0 .. T - 2;  snap_dev <- counts_dev;  kappa = lag / (time (m - 1 + lag))
+ *     g_i = (1 / beta_i - 1 / beta_{i-1}) exp(kappa (A_{i-1} - A_i)),  1 / beta_i = 1 + g_1 + ... + g_i (index order), i = 1 .. T - 2
+ * betas_dev[0] and betas_dev[T - 1] (= 0, required of the caller: the hot end at infinite temperature) are never written;
+ * history_dev [., T] row m <- the new ladder (row 0 is the caller's).  T >= 3.  Only enqueues. */
+int asmc_pt_steps_supported(int d, int x_dtype, const void* x_dev);
+int asmc_pt_pack(asmc_ctx* ctx, int n_temps, int64_t n_walkers, const asmc_pcn_params* params, const double* const* mu_dev,
+                 const double* const* L_dev, const double* const* Linv_dev, const double* nu_host, asmc_stream stream);
+int asmc_pt_steps(asmc_ctx* ctx, int n_temps, int64_t n_walkers, void* x_dev, double* ll_dev, double* lp_dev, double* lq_dev,
+                  const asmc_pcn_params* params, const double* betas_dev, double* rho_dev, int64_t* accept_dev, int n_steps,
+                  uint32_t step0, const asmc_chain_target* chain, int64_t slot0, asmc_stream stream);
+int asmc_pt_ladder_adapt(asmc_ctx* ctx, int n_temps, int64_t n_walkers, const int64_t* counts_dev, int64_t* snap_dev,
+                         double* betas_dev, double* history_dev, int update, double lag, double time, asmc_stream stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,10 @@ warm-up pair (tools/bench_mcmc.py).  The exchange kernel's time is the library's
 swap_every = 1; its traffic is 2 rows read and 2 written per accepted pair plus the two log-likelihoods every pair reads.  The
 evidence reductions are timed on the full recorded chain of the S2 run (wall time of the call, which ends in its one
 synchronisation) next to asmc_weights_stats on three arrays of the same total size.  Prints one JSON line.
-Env: T, W, S1, S2, REPS, STEP_FN=pcn|tpcn."""
+Env: T, W, S1, S2, REPS, STEP_FN=pcn|tpcn.
+--rung-launch per_rung|batched: how the rungs' steps are launched; --adapt-ladder: the ladder adapts until
+the last step of the run (batched only; swap_every = 1 alone is timed); --rounds-only: the per-round times alone."""
+import argparse
 import json
 import os
 import statistics
@@ -42,9 +45,13 @@ def timed(fn):
     return time.perf_counter() - t0, out
 
 
+LAUNCH = {}  # the sampler keywords the command line adds
+
+
 def pt_run(eng, n_temps, w, steps, swap_every, step_fn):
     s = sampler(HipPTMiniPCN, eng)
-    dt, out = timed(lambda: s.sample(n_walkers=w, n_temps=n_temps, n_steps=steps, swap_every=swap_every, step_fn=step_fn))
+    kw = dict(LAUNCH, burnin=steps - 1) if LAUNCH.get("adapt_ladder") else LAUNCH  # (the ladder moves through all but the last step)
+    dt, out = timed(lambda: s.sample(n_walkers=w, n_temps=n_temps, n_steps=steps, swap_every=swap_every, step_fn=step_fn, **kw))
     return dt, s, out
 
 
@@ -70,11 +77,19 @@ def per_step(run, s1, s2, reps):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rung-launch", choices=("per_rung", "batched"), default="per_rung")
+    ap.add_argument("--adapt-ladder", action="store_true")
+    ap.add_argument("--rounds-only", action="store_true")
+    args = ap.parse_args()
+    LAUNCH.update(rung_launch=args.rung_launch)
+    if args.adapt_ladder:
+        LAUNCH.update(adapt_ladder=True)
     n_temps, w = int(os.environ.get("T", 8)), int(os.environ.get("W", 1 << 17))
     s1, s2, reps = int(os.environ.get("S1", 8)), int(os.environ.get("S2", 40)), int(os.environ.get("REPS", 3))
     step_fn = os.environ.get("STEP_FN", "tpcn")
     eng = HipEngine(0, n_max=n_temps * w, d_max=D)
-    res = {"n_temps": n_temps, "n_walkers": w, "d": D, "step_fn": step_fn}
+    res = {"n_temps": n_temps, "n_walkers": w, "d": D, "step_fn": step_fn, "rung_launch": args.rung_launch, "adapt_ladder": args.adapt_ladder}
 
     def pt_time(swap_every):
         def run(steps):
@@ -84,8 +99,11 @@ def main():
             return dt
         return per_step(run, s1, s2, reps)
 
-    for k in (0, 1, 8):
+    for k in ((1,) if args.adapt_ladder else (0, 1, 8)):
         res[f"ms_per_step_swap_every_{k}"] = round(1e3 * pt_time(k), 4)
+    if args.rounds_only:
+        print(json.dumps(res))
+        return
     res["ms_per_step_independent_minipcn"] = round(1e3 * per_step(lambda steps: independent_run(eng, n_temps, w, steps, step_fn), s1, s2, reps), 4)
 
     # the exchange kernel at the acceptance of a real run
