@@ -26,7 +26,7 @@ COUNT_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 ASMC_BIS_REC = 40
 ASMC_SELECT_THREADS = 262144
 ASMC_STUDENT_MAX_ROWS = 16384
-ASMC_ABI_VERSION = 30
+ASMC_ABI_VERSION = 31
 ASMC_FLOW_COUPLING, ASMC_FLOW_MAF = 0, 1  # asmc_coupling.kind
 ASMC_MAX_COUNT_CELLS = 64  # asmc_pcn_set_count_cells
 ASMC_CDF_REC = 9
@@ -37,6 +37,7 @@ ASMC_NUTS_VEC_Z, ASMC_NUTS_VEC_POINT, ASMC_NUTS_VEC_GRAD, ASMC_NUTS_VEC_FIXED = 
 ASMC_NUTS_SC_DENSITIES, ASMC_NUTS_SC_SLOTS, ASMC_NUTS_INT_SLOTS = 4, 10, 12
 ASMC_CHAIN_ROWS, ASMC_CHAIN_YS = 0, 1  # asmc_chain_record: source
 ASMC_PT_MAX_RUNGS = 64  # asmc_pt_swap / asmc_pt_evidence
+ASMC_DIAG_KB = 32  # lags per asmc_chain_acf_block call (what asmc_chain_acf_kb returns)
 
 
 class AsmcMixture(ctypes.Structure):
@@ -298,6 +299,12 @@ SIGNATURES = {
     "asmc_pt_steps": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, POINTER(AsmcPcnParams), _vp, _vp, _vp, _i, _u32, POINTER(AsmcChainTarget),
                            _i64, _vp]),
     "asmc_pt_ladder_adapt": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _d, _d, _vp]),
+    "asmc_chain_acf_kb": (_i, []),
+    "asmc_chain_acf_blocks": (_i, [_i64, _i]),
+    "asmc_chain_series_moments": (_i, [_vp, _i, _vp, _i64, _i64, _i, _i64, _i, _vp, _vp, _vp]),
+    "asmc_chain_acf_block": (_i, [_vp, _i, _vp, _i64, _i64, _i, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
+    "asmc_chain_acf_finish": (_i, [_vp, _i64, _i64, _i, _i64, _i, _d, _vp, _vp, _vp, _i64, _vp]),
+    "asmc_chain_rhat": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1278,6 +1278,51 @@ class HipEngine:
     def chain_clear(self):
         check(self.lib.asmc_chain_clear(self._ctx), "asmc_chain_clear")
 
+    # ---- diagnostics of a recorded chain (include/asmc.h asmc_chain_series_moments / _acf_* / _rhat) -----------------
+    def _chain_view(self, chain_x):
+        assert chain_x.dim() == 3 and chain_x.is_contiguous() and chain_x.device == self.device, \
+            "a contiguous chain [n_steps, n_walkers, d] on the engine's device"
+        S, W, d = (int(v) for v in chain_x.shape)
+        return S, W, d, self._xdt(chain_x)
+
+    def chain_autocorr(self, chain_x, c: float = 5.0, return_rho: bool = False, kb: int | None = None):
+        """emcee's integrated autocorrelation time of a recorded chain [n_steps, n_walkers, d] (`DeviceChain.x`, a slice of its
+        steps, or one rung of a tempered chain [T, S, W, d]), read where it lies: (tau [d], window [d]) as numpy arrays, and with
+        `return_rho` the walker-averaged autocorrelation function rho [d, n_steps] as well (NaN behind each coordinate's window).
+        Lag blocks of `kb` lags (ASMC_DIAG_KB) run until every coordinate has found its window; the d done flags are read back
+        after each block - one small synchronisation per block.  Scratch from `empty`: 2 W d doubles for the series' moments -
+        512 MB at 1M walkers x 32 dimensions - plus blocks x d x kb doubles of partials (at most 2048 blocks)."""
+        S, W, d, xdt = self._chain_view(chain_x)
+        kb = int(kb or _lib.ASMC_DIAG_KB)
+        mom = self.empty((2, W * d))
+        part = self.empty((int(self.lib.asmc_chain_acf_blocks(W, d)), d, kb))
+        state = self.empty((4, d))
+        rho = torch.full((d, S), float("nan"), dtype=torch.float64, device=self.device) if return_rho else None
+        check(self.lib.asmc_chain_series_moments(self._ctx, xdt, _dptr(chain_x), S, W, d, d, 0, _dptr(mom[0]), _dptr(mom[1]),
+                                                 self._stream), "asmc_chain_series_moments")
+        for k0 in range(0, S, kb):
+            check(self.lib.asmc_chain_acf_block(self._ctx, xdt, _dptr(chain_x), S, W, d, d, k0, kb, _dptr(mom[0]), _dptr(mom[1]),
+                                                _dptr(part), self._stream), "asmc_chain_acf_block")
+            check(self.lib.asmc_chain_acf_finish(self._ctx, S, W, d, k0, kb, float(c), _dptr(part), _dptr(state), _dptr(rho), S,
+                                                 self._stream), "asmc_chain_acf_finish")
+            host = state.cpu().numpy()
+            if host[1].all():
+                break
+        assert host[1].all()  # (the block with lag S - 1 finishes every coordinate)
+        out = (host[3].copy(), host[2].astype(np.int64))
+        return out + (rho.cpu().numpy(),) if return_rho else out
+
+    def chain_rhat(self, chain_x) -> np.ndarray:
+        """Split R-hat per coordinate (Gelman et al., BDA3 §11.4) of a recorded chain [n_steps, n_walkers, d]: every walker's
+        series is split into its first and last n_steps // 2 steps.  Scratch: 4 W d doubles."""
+        S, W, d, xdt = self._chain_view(chain_x)
+        mom = self.empty((2, 2, W * d))
+        out = self.empty(d)
+        check(self.lib.asmc_chain_series_moments(self._ctx, xdt, _dptr(chain_x), S, W, d, d, 1, _dptr(mom[0]), _dptr(mom[1]),
+                                                 self._stream), "asmc_chain_series_moments")
+        check(self.lib.asmc_chain_rhat(self._ctx, S, W, d, _dptr(mom[0]), _dptr(mom[1]), _dptr(out), self._stream), "asmc_chain_rhat")
+        return out.cpu().numpy()
+
     # ---- parallel tempering of the "pt_minipcn" sampler (include/asmc.h asmc_pt_*) ---------------------------------------------------
     def pt_swap(self, x, ll, lp, betas, seed: int, rnd: int, counts, c0=None, c1=None):
         """Replica exchange round `rnd` on the state of len(betas) rungs (x [T W, d], rung r in rows r W .. (r + 1) W; ll, lp and

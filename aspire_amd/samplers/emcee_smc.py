@@ -40,6 +40,17 @@ def stretch_move_settings(moves) -> tuple[float, bool]:
     return a, bool(getattr(moves, "live_dangerously", False))
 
 
+def autocorr_length_check(tau: np.ndarray, n_t: int, tol: float, quiet: bool) -> None:
+    """emcee's rule on an estimate `tau` from `n_t` steps: tol tau > n_t logs its warning (quiet) or raises."""
+    flag = tol * np.asarray(tau) > n_t
+    if np.any(flag):
+        msg = (f"The chain is shorter than {tol} times the integrated autocorrelation time for {int(np.sum(flag))} parameter(s). "
+               f"Use this estimate with caution and run a longer chain!\nN/{tol} = {n_t / tol:.0f};\ntau: {tau}")
+        if not quiet:
+            raise RuntimeError(msg)
+        logger.warning(msg)
+
+
 def integrated_time(x: np.ndarray, c: float = 5, tol: float = 50, quiet: bool = False) -> np.ndarray:
     """emcee.autocorr.integrated_time of a chain [n_steps, n_walkers, d]: per coordinate, the FFT autocorrelation of every
     walker's chain, averaged over the walkers, taus = 2 cumsum(f) - 1, Sokal's window (the first lag with lag >= c tau).  A chain
@@ -57,13 +68,7 @@ def integrated_time(x: np.ndarray, c: float = 5, tol: float = 50, quiet: bool = 
         m = np.arange(n_t)[:, None] < c * taus
     windows = np.where(m.any(axis=0), np.argmin(m, axis=0), n_t - 1)
     tau = taus[windows, np.arange(n_d)]
-    flag = tol * tau > n_t
-    if np.any(flag):
-        msg = (f"The chain is shorter than {tol} times the integrated autocorrelation time for {int(np.sum(flag))} parameter(s). "
-               f"Use this estimate with caution and run a longer chain!\nN/{tol} = {n_t / tol:.0f};\ntau: {tau}")
-        if not quiet:
-            raise RuntimeError(msg)
-        logger.warning(msg)
+    autocorr_length_check(tau, n_t, tol, quiet)
     return tau
 
 

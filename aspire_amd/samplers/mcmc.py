@@ -31,6 +31,31 @@ class ChainSampler(MCMCSampler):
     """What the two samplers share: one rank only, the memory guard, the preconditioned start, the containers."""
 
     last_mutation_path = None
+    _last_chain = None  # the whole chain of the last run as a device container: what get_autocorr_time reduces
+
+    def get_autocorr_time(self, discard: int = 0, thin: int = 1, c: float = 5, tol: float = 50, quiet: bool = False):
+        """emcee's `EnsembleSampler.get_autocorr_time` over the chain of the last run: the integrated autocorrelation time per
+        coordinate ([d]; the tempered sampler: one row per rung) of the steps `get_chain(discard, thin)` keeps, times `thin`,
+        reduced on the device where the chain lies.  A chain shorter than `tol` tau raises, or logs a warning
+        when `quiet`.  The one deviation from emcee: emcee estimates on its own chain, which lives in the preconditioned space;
+        this is the recorded chain, in x.  The sampler keeps the last run's chain alive on the device for this call."""
+        from .emcee_smc import autocorr_length_check
+
+        if self._last_chain is None:
+            raise RuntimeError(f"{type(self).__name__}.get_autocorr_time needs a recorded chain: call sample() first "
+                               "(without last_step_only)")
+        full, discard, thin = self._last_chain, int(discard), int(thin)
+        tau = full._tau(c, discard, thin)
+        autocorr_length_check(tau, len(range(discard + thin - 1, full._rungs()[0].shape[0], thin)), tol, quiet)
+        return thin * tau
+
+    def _keep_chain(self, full, autocorr: bool, discard: int = 0):
+        """Remember the run's device container; with `autocorr` fill its `autocorrelation_time` (emcee's defaults, quiet) over
+        the steps behind `discard`."""
+        self._last_chain = full
+        if autocorr:
+            full.integrated_autocorr_time(quiet=True, discard=discard)
+        return full
 
     def _single_rank(self):
         if self.comm.sharded:
@@ -103,8 +128,12 @@ class HipMiniPCN(ChainSampler):
     @track_calls
     def sample(self, n_samples: int | None = None, n_walkers: int | None = None, rng=None, target_acceptance_rate=0.234,
                n_steps=100, thin=1, burnin=0, last_step_only=False, step_fn="tpcn", checkpoint_callback=None,
-               checkpoint_every: int | None = None, checkpoint_file_path: str | None = None):
+               checkpoint_every: int | None = None, checkpoint_file_path: str | None = None, autocorr: bool = False):
+        """`autocorr`: the returned container arrives with `autocorrelation_time` filled, from the steps behind `burnin` (in
+        steps of the unthinned chain)."""
         self._single_rank()
+        if autocorr and last_step_only:
+            raise ValueError("autocorr=True needs the recorded chain: not with last_step_only=True")
         if step_fn not in ("pcn", "tpcn"):
             raise NotImplementedError(f"step_fn={step_fn!r} is not implemented by the HIP step kernels; use step_fn='tpcn' or 'pcn'")
         e = self.engine
@@ -135,13 +164,15 @@ class HipMiniPCN(ChainSampler):
         self._check_reference_fit()
         self.history.mcmc_acceptance.append(float(np.mean(acc)) / n_walkers)
         self.history.mcmc_step_size.append(float(self._pcn_state["rho"]))
+        self._last_chain = None
         if last_step_only:
             x = z if T is None else e.asarray(T.inverse(z)[0], dtype=z.dtype)
             out = Samples(x=x, xp=torch, parameters=self.parameters)
             out.log_likelihood, out.log_prior = ll, lp  # (set afterwards: no importance weights)
             return self._out(out)
-        full = self._out(MCMCSamples.from_chain(chain=chain.x, log_likelihood=chain.ll, log_prior=chain.lp, parameters=self.parameters,
-                                                xp=torch, dtype=self.dtype, thin=1, burn_in=0))
+        full = MCMCSamples.from_chain(chain=chain.x, log_likelihood=chain.ll, log_prior=chain.lp, parameters=self.parameters,
+                                      xp=torch, dtype=self.dtype, thin=1, burn_in=0, engine=e)
+        full = self._out(self._keep_chain(full, autocorr, int(burnin)))
         self.checkpoint_mcmc_chain(samples=full, iteration=n_steps, checkpoint_callback=checkpoint_callback,
                                    checkpoint_every=checkpoint_every, checkpoint_file_path=checkpoint_file_path)
         out = full.post_process(burn_in=burnin, thin=thin)
@@ -232,7 +263,9 @@ class HipEmcee(ChainSampler):
 
     @track_calls
     def sample(self, n_samples: int | None = None, nwalkers: int | None = None, nsteps: int = 500, rng=None, discard=0,
-               checkpoint_callback=None, checkpoint_every: int | None = None, checkpoint_file_path: str | None = None, **kwargs):
+               checkpoint_callback=None, checkpoint_every: int | None = None, checkpoint_file_path: str | None = None,
+               autocorr: bool = False, **kwargs):
+        """`autocorr`: the returned container arrives with `autocorrelation_time` filled, from the kept steps."""
         self._single_rank()
         unknown = sorted(set(kwargs) - set(EMCEE_KWARGS))
         if unknown:
@@ -269,8 +302,9 @@ class HipEmcee(ChainSampler):
                     self._record(chain, t - discard, z, ll, lp, T)
             accepted += int(e.stretch_counts(chunk).sum())
         self.history.mcmc_acceptance.append(float(accepted / (nwalkers * nsteps)))
-        out = self._out(MCMCSamples.from_chain(chain=chain.x, log_likelihood=chain.ll, log_prior=chain.lp, parameters=self.parameters,
-                                               xp=torch, dtype=self.dtype, burn_in=discard))
+        out = MCMCSamples.from_chain(chain=chain.x, log_likelihood=chain.ll, log_prior=chain.lp, parameters=self.parameters,
+                                     xp=torch, dtype=self.dtype, burn_in=discard, engine=e)
+        out = self._out(self._keep_chain(out, autocorr))
         self.checkpoint_mcmc_chain(samples=out, iteration=nsteps, checkpoint_callback=checkpoint_callback,
                                    checkpoint_every=checkpoint_every, checkpoint_file_path=checkpoint_file_path)
         if n_samples is not None:
@@ -350,7 +384,10 @@ class HipPTMiniPCN(ChainSampler):
                n_steps: int = 100, swap_every: int = 1, burnin: int = 0, thin: int = 1, step_fn: str = "tpcn",
                target_acceptance_rate: float = 0.234, refit_every: int | None = None, rng=None, checkpoint_callback=None,
                checkpoint_every: int | None = None, checkpoint_file_path: str | None = None, rung_launch: str = "per_rung",
-               adapt_ladder: bool = False, ladder_lag: float = LADDER_LAG, ladder_time: float = LADDER_TIME, noise: str = "f64"):
+               adapt_ladder: bool = False, ladder_lag: float = LADDER_LAG, ladder_time: float = LADDER_TIME, noise: str = "f64",
+               autocorr: bool = False):
+        """`autocorr`: the returned container arrives with `autocorrelation_time` [n_temps, d] filled, from the steps behind
+        `burnin` (in steps of the unthinned chain); the cold rung's row is appended to `history.mcmc_autocorr`."""
         self._single_rank()
         if step_fn not in ("pcn", "tpcn"):
             raise NotImplementedError(f"step_fn={step_fn!r} is not implemented by the HIP step kernels; use step_fn='tpcn' or 'pcn'")
@@ -513,6 +550,9 @@ class HipPTMiniPCN(ChainSampler):
         else:
             self.evidence = {"thermodynamic_integration": full.log_evidence_thermodynamic_integration(),
                              "stepping_stone": full.log_evidence_stepping_stone() if ladder[-1] == 0.0 else None}
+        self._keep_chain(full, autocorr, int(burnin))
+        if autocorr:
+            self.history.mcmc_autocorr.append(np.asarray(full.autocorrelation_time[0], dtype=np.float64).copy())
         full = self._out(full)
         self.checkpoint_mcmc_chain(samples=full, iteration=n_steps, checkpoint_callback=checkpoint_callback,
                                    checkpoint_every=checkpoint_every, checkpoint_file_path=checkpoint_file_path)

@@ -369,6 +369,7 @@ class MCMCSamples(BaseSamples):
     thin: int | None = None
     burn_in: int | None = None
     autocorrelation_time: Any | None = None
+    engine: Any = field(default=None, repr=False, compare=False)
 
     def __post_init__(self):
         super().__post_init__()
@@ -416,7 +417,7 @@ class MCMCSamples(BaseSamples):
 
     def _extra_kwargs(self, conv=None) -> dict:
         """Constructor arguments of a subclass that travel through post_process / to_numpy / to_namespace."""
-        return {}
+        return {"engine": self.engine}
 
     def post_process(self, burn_in: int = 0, thin: int = 1) -> "MCMCSamples":
         """Drop the first `burn_in` steps and keep every `thin`-th of the rest; the metadata accumulate (thin multiplies,
@@ -457,12 +458,94 @@ class MCMCSamples(BaseSamples):
                               log_prior=conv(self.log_prior), log_q=conv(self.log_q), xp=xp, dtype=dtype, chain_shape=self.chain_shape,
                               **self._meta(), **self._extra_kwargs(conv))
 
+    # ---- diagnostics ------------------------------------------------------------------------------------
+    def _rungs(self):
+        """The chains the diagnostics run over, each [n_steps, n_walkers, d]; a flat chain [n_steps] is one walker."""
+        chain = self.chain
+        if chain.ndim == 2:
+            chain = chain.reshape(chain.shape[0], 1, chain.shape[1])
+        if chain.ndim != 3:
+            raise ValueError(f"the diagnostics need a chain [n_steps, n_walkers, d], got {tuple(chain.shape)}")
+        return [chain]
+
+    def _stack(self, rows):
+        return rows[0]
+
+    def _chain_engine(self):
+        return self.engine if self.engine is not None else get_default_engine()
+
+    def integrated_autocorr_time(self, c: float = 5, tol: float = 50, quiet: bool = True, discard: int = 0):
+        """emcee's integrated autocorrelation time per coordinate ([d]; one row per rung of a tempered chain) over the steps
+        behind `discard`, stored in `autocorrelation_time` and returned.  A chain shorter than `tol` tau raises (logs a warning
+        when `quiet`), with emcee's message.  Device tensors are reduced by the engine where they lie (`chain_autocorr`); numpy
+        arrays go through the host estimator `integrated_time`."""
+        from .samplers.emcee_smc import autocorr_length_check
+
+        tau = self._tau(c, discard)
+        autocorr_length_check(tau, self._rungs()[0].shape[0] - int(discard), tol, quiet)
+        self.autocorrelation_time = tau
+        return tau
+
+    def _tau(self, c: float = 5, discard: int = 0, thin: int = 1):
+        """tau of the steps discard + thin - 1, discard + 2 thin - 1, ... (emcee's get_chain(discard, thin)), not stored.  The kept
+        steps of an unthinned chain are read in place; a thinned device chain is copied first."""
+        from .samplers.emcee_smc import integrated_time
+
+        discard, thin = int(discard), int(thin)
+        rungs = self._rungs()
+        if thin < 1 or not 0 <= discard + thin - 1 < rungs[0].shape[0]:
+            raise ValueError(f"discard = {discard}, thin = {thin} leave no step of {rungs[0].shape[0]}")
+        rows = []
+        for chain in rungs:
+            kept = chain[discard + thin - 1::thin]
+            if is_torch(kept):
+                tau = self._chain_engine().chain_autocorr(kept.contiguous(), c=float(c))[0]
+            else:
+                tau = integrated_time(np.asarray(kept), c=c, tol=0, quiet=True)
+            rows.append(np.asarray(tau, dtype=np.float64))
+        return self._stack(rows)
+
+    def effective_sample_size(self):
+        """n_steps n_walkers / tau per coordinate (tau is computed with the defaults when it is not there yet)."""
+        tau = self.autocorrelation_time if self.autocorrelation_time is not None else self.integrated_autocorr_time()
+        chain = self._rungs()[0]
+        return chain.shape[0] * chain.shape[1] / np.asarray(to_numpy(tau), dtype=np.float64)
+
+    def split_rhat(self):
+        """Split R-hat per coordinate (Gelman et al., BDA3 §11.4): every walker's series split into its first and last
+        n_steps // 2 steps.  Device tensors by `chain_rhat`, numpy arrays by `split_rhat_host`."""
+        rows = []
+        for chain in self._rungs():
+            if is_torch(chain):
+                rows.append(np.asarray(self._chain_engine().chain_rhat(chain.contiguous()), dtype=np.float64))
+            else:
+                rows.append(split_rhat_host(np.asarray(chain)))
+        return self._stack(rows)
+
     def _encode_for_hdf5(self, flat: bool = True) -> dict:
         d = super()._encode_for_hdf5(flat=flat)
         d["chain_shape"] = np.asarray(self.chain_shape, dtype=np.int64)  # (a tuple of ints has no dataset form of its own)
         if d.get("autocorrelation_time") is not None:
             d["autocorrelation_time"] = to_numpy(d["autocorrelation_time"])
         return d
+
+
+def split_rhat_host(chain: np.ndarray) -> np.ndarray:
+    """Split R-hat of a chain [n_steps, n_walkers, d] in fp64: the m = 2 n_walkers half-chains of length n = n_steps // 2 (an odd
+    chain drops its middle step), B = n / (m - 1) sum (mean_c - mean)^2, W = mean of the sample variances,
+    sqrt(((n - 1) / n W + B / n) / W).  n < 2 gives NaN."""
+    x = np.asarray(chain, dtype=np.float64)
+    n_t, _, n_d = x.shape
+    n = n_t // 2
+    if n < 2:
+        return np.full(n_d, np.nan)
+    halves = np.concatenate((x[:n], x[n_t - n:]), axis=1)  # [n, m, d]
+    m = halves.shape[1]
+    means = halves.mean(axis=0)
+    b = n / (m - 1) * np.sum((means - means.mean(axis=0)) ** 2, axis=0)
+    w = np.mean(np.sum((halves - means) ** 2, axis=0) / (n - 1), axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.sqrt(((n - 1) / n * w + b / n) / w)
 
 
 _trapezoid = getattr(np, "trapezoid", None) or np.trapz
@@ -510,10 +593,23 @@ class PTMCMCSamples(MCMCSamples):
         return (slice(None), slice(burn_in, None, thin))  # the step axis is the second one
 
     def _extra_kwargs(self, conv=None) -> dict:
-        return {"betas": self.betas if conv is None or self.betas is None else conv(self.betas)}
+        return {"betas": self.betas if conv is None or self.betas is None else conv(self.betas), "engine": self.engine}
 
     def _per_row(self, v):
         return None if v is None else v.reshape(self.chain_shape)
+
+    def _rungs(self):
+        chain = self.chain
+        if chain.ndim != 4:
+            raise ValueError(f"the diagnostics need a chain [n_temps, n_steps, n_walkers, d], got {tuple(chain.shape)}")
+        return [chain[r] for r in range(chain.shape[0])]
+
+    def _stack(self, rows):
+        return np.stack(rows)  # [n_temps, d]: what at_temperature indexes
+
+    def effective_sample_size(self):
+        tau = self.autocorrelation_time if self.autocorrelation_time is not None else self.integrated_autocorr_time()
+        return self.chain_shape[1] * self.chain_shape[2] / np.asarray(to_numpy(tau), dtype=np.float64)
 
     def at_temperature(self, index: int) -> MCMCSamples:
         """Rung `index` as a plain MCMCSamples."""

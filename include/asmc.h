@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 30
+#define ASMC_ABI_VERSION 31
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -1073,6 +1073,49 @@ int asmc_pt_steps(asmc_ctx* ctx, int n_temps, int64_t n_walkers, void* x_dev, do
                   uint32_t step0, const asmc_chain_target* chain, int64_t slot0, asmc_stream stream);
 int asmc_pt_ladder_adapt(asmc_ctx* ctx, int n_temps, int64_t n_walkers, const int64_t* counts_dev, int64_t* snap_dev,
                          double* betas_dev, double* history_dev, int update, double lag, double time, asmc_stream stream);
+
+/* ---- diagnostics of a recorded chain (ABI 31) ------------------------------------------------------------
+ * A chain is x_dev [n_steps, n_walkers, pitch] of x_dtype, element (t, w, j) at t W pitch + w pitch + j - the layout of
+ * asmc_chain_target, from a pointer to the first KEPT step: discarding steps, or taking rung r of a tempered chain [T, S, W, d], is
+ * pointer arithmetic of the caller, never a copy.  Nothing outside these n_steps steps is read.  A series is one coordinate of one
+ * walker, number w d + j.  All sums are fp64 whatever x_dtype is, every index is 64-bit, and there are no floating-point atomics:
+ * sums across walkers are block partials (walker order) added by a finishing kernel (block order), so two runs give the same bits.
+ * Every entry point only enqueues: no synchronisation, no allocation.  Errors (ASMC_ERR_ARG): a null pointer, n_steps < 1,
+ * n_walkers < 1, d outside 1 .. ASMC_MAX_DIMS, pitch outside d .. 2^20, a bad x_dtype, kb other than 16 / 32, k0 no multiple of kb.
+ *
+ * asmc_chain_series_moments: halves = 0: mean_dev / c0_dev [W d] <- per series the mean m over the n_steps steps and
+ *   c0 = sum (x - m)^2.  halves = 1: mean_dev / c0_dev [2, W d] <- the same over the first (row 0) and the last (row 1)
+ *   n_steps / 2 steps, what split R-hat needs; an odd n_steps drops its middle step, n_steps = 1 gives NaN means.
+ *
+ * asmc_chain_acf_block: the lags k = k0 .. k0 + kb - 1 (kb = 16 or 32; ASMC_DIAG_KB is what asmc_chain_acf_kb returns and the
+ *   package uses).  With the halves = 0 moments, per series a[k] = sum_{t = 0}^{S - 1 - k} (x_t - m)(x_{t+k} - m) / c0 - emcee's
+ *   zero-padded FFT autocorrelation function, no 1 / (S - k) factor; lags >= S give 0; c0 = 0 gives NaN - summed over the walkers
+ *   of a block into partials_dev [asmc_chain_acf_blocks(W, d), d, kb].  One sweep over the steps per call: the chain is read twice
+ *   (leading and trailing stream), kb fused multiply-adds per element.
+ *
+ * asmc_chain_acf_finish: rho_j[k] = (1 / W) sum of the partials, for the block's lags in order; advances state_dev [4, d] =
+ *   {running sum of rho_j | done (0 / 1) | window | tau}: tau_k = 2 sum_{i <= k} rho_j[i] - 1, the window is the first lag with
+ *   k >= c tau_k, or n_steps - 1 when there is none (emcee's auto_window); a NaN rho finishes the coordinate at once with tau =
+ *   NaN and window n_steps - 1.  The call with k0 = 0 initialises the state itself.  A finished coordinate is not touched again.
+ *   rho_dev (or NULL) [d, rho_pitch >= n_steps]: rho_j[k] is written for the lags up to the window.  The caller reads the done
+ *   flags back after a block and stops when all are set, or after the block that holds lag n_steps - 1.
+ *
+ * asmc_chain_rhat: split R-hat (Gelman et al., BDA3 section 11.4) from the halves = 1 moments: m = 2 W half-chains of length
+ *   n = n_steps / 2, B = n / (m - 1) sum (mean_c - mean)^2, Wv = mean of the sample variances c0_c / (n - 1),
+ *   rhat_dev [d] <- sqrt(((n - 1) / n Wv + B / n) / Wv); the grand mean first, then the squared deviations and the variances,
+ *   each stage as block partials over the half-chains (in the context's block-partial scratch) and a finishing launch that adds
+ *   them in block order: four launches.  n < 2 gives NaN. */
+#define ASMC_DIAG_KB 32
+int asmc_chain_acf_kb(void);
+int asmc_chain_acf_blocks(int64_t n_walkers, int d);
+int asmc_chain_series_moments(asmc_ctx* ctx, int x_dtype, const void* x_dev, int64_t n_steps, int64_t n_walkers, int d, int64_t pitch,
+                              int halves, double* mean_dev, double* c0_dev, asmc_stream stream);
+int asmc_chain_acf_block(asmc_ctx* ctx, int x_dtype, const void* x_dev, int64_t n_steps, int64_t n_walkers, int d, int64_t pitch,
+                         int64_t k0, int kb, const double* mean_dev, const double* c0_dev, double* partials_dev, asmc_stream stream);
+int asmc_chain_acf_finish(asmc_ctx* ctx, int64_t n_steps, int64_t n_walkers, int d, int64_t k0, int kb, double c,
+                          const double* partials_dev, double* state_dev, double* rho_dev, int64_t rho_pitch, asmc_stream stream);
+int asmc_chain_rhat(asmc_ctx* ctx, int64_t n_steps, int64_t n_walkers, int d, const double* half_mean_dev, const double* half_c0_dev,
+                    double* rhat_dev, asmc_stream stream);
 
 #ifdef __cplusplus
 }
