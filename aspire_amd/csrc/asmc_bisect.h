@@ -1,6 +1,6 @@
 // Decision half of the adaptive-temperature search (reference: src/aspire/samplers/smc/base.py:167-186) - what closes a
 // round of 16 candidate temperatures and chooses the next 16.  Plain C++ (host and device): the HIP kernels call it from
-// one lane behind their reductions (asmc_weights.hip: k_bis_sums' last block, k_bis_decide, k_is_weights), and
+// one lane behind their reductions (asmc_search_dev.h: k_bis_sums' last block, k_bis_decide, k_is_weights), and
 // tests/tools/bisect_plan_check.cpp drives it on the CPU against the sequential loop.
 //
 // The reference bisects [beta0, 1] until the bracket is no wider than the tolerance and returns its lower end: with a
@@ -30,11 +30,21 @@
 #define BIS_HD inline
 #endif
 
-// state record (doubles); [0..15] and [32..39] as in rounds 1-2, [16..31] are this file's
+// The state record of a search: BIS_STATE_LEN doubles.  This is its one description; the kernels and the host calls index it by
+// these names only.  [0..15] and [32..39] as in rounds 1-2, [16..31] are this file's.
 enum {
-    BIS_BMIN = 0, BIS_BMAX = 1, BIS_DONE = 2, BIS_TARGET = 3, BIS_TOL = 4, BIS_LOGN = 5, BIS_ROUNDS = 6, BIS_BETA0 = 7,
-    BIS_N = 8, BIS_EFF_ONE = 9, BIS_M_ONE = 10, BIS_TRIP_M = 11, BIS_TRIP_S1 = 12, BIS_TRIP_S2 = 13, BIS_TRIP_OK = 14,
-    BIS_NAN = 15,
+    BIS_BMIN = 0, BIS_BMAX = 1,  // the bracket's floats; beta_min is beta* once done
+    BIS_DONE = 2,                // 1: the search has ended
+    BIS_TARGET = 3, BIS_TOL = 4, // target ESS/N, tolerance on the bracket's width
+    BIS_LOGN = 5,                // log N
+    BIS_ROUNDS = 6,              // rounds closed so far
+    BIS_BETA0 = 7,               // the temperature the population is at
+    BIS_N = 8,
+    BIS_EFF_ONE = 9,             // ESS(1)/N
+    BIS_M_ONE = 10,              // m(1): the maximum of the log-weights at beta = 1
+    BIS_TRIP_M = 11, BIS_TRIP_S1 = 12, BIS_TRIP_S2 = 13,  // (m, S1, S2) of the log-sum-exp at beta_min ...
+    BIS_TRIP_OK = 14,            // ... 1 when they are valid
+    BIS_NAN = 15,                // NaN log-weights (the merged census: k_is_weights and the sharded search)
     BIS_LU = 16,      // level of the index unit
     BIS_LFIN = 17,    // level at which the reference's loop stops
     BIS_KLO = 18, BIS_KHI = 19,        // bracket: ESS(K_lo) >= target > ESS(K_hi)
@@ -43,13 +53,25 @@ enum {
     BIS_MODE = 24,    // 1: plain steps only (a window has missed)
     BIS_WINDOW = 25,  // 1: the grid of [20], [21] is a prediction window
     BIS_WINDOWS = 26, BIS_MISSES = 27,  // statistics: windows evaluated, windows that missed
-    BIS_S1_ONE = 32, BIS_S2_ONE = 33,
-    BIS_C1 = 34, BIS_C2 = 35, BIS_M1 = 36, BIS_H = 37, BIS_DMAX = 38,  // the next grid for the sums kernels
-    BIS_NEWPACK = 39
+    BIS_S1_ONE = 32, BIS_S2_ONE = 33,  // S1(1), S2(1)
+    // the next grid for the sums kernels: c1, c2 and the log-sum-exp shift m of the LOWEST candidate, spacing h, Delta_max
+    BIS_C1 = 34, BIS_C2 = 35, BIS_M1 = 36, BIS_H = 37, BIS_DMAX = 38,
+    BIS_NEWPACK = 39,  // 1: this round chose a new candidate grid
+    BIS_STATE_LEN = 40
 };
 
 // sorted candidate j (ascending beta) -> column pair of the partial records (the heap order of the first round's tree)
-BIS_HD int bis_col_of_sorted(int j) { return (int)((0xFE6D2C5B0A491837ULL >> (4 * j)) & 15ULL); }
+BIS_HD constexpr int bis_col_of_sorted(int j) { return (int)((0xFE6D2C5B0A491837ULL >> (4 * j)) & 15ULL); }
+// its inverse: heap column k -> sorted position
+BIS_HD constexpr int bis_sorted_of_col(int k) { return (int)((0xFECA86420D951B37ULL >> (4 * k)) & 15ULL); }
+// the two packed tables against the in-order walk of the four-level heap written out (node 15: the bracket's upper end)
+constexpr bool bis_perm_agrees() {
+    const int heap_of_sorted[16] = {7, 3, 8, 1, 9, 4, 10, 0, 11, 5, 12, 2, 13, 6, 14, 15};
+    for (int j = 0; j < 16; j++)
+        if (bis_col_of_sorted(j) != heap_of_sorted[j] || bis_sorted_of_col(heap_of_sorted[j]) != j) return false;
+    return true;
+}
+static_assert(bis_perm_agrees(), "bis_col_of_sorted, bis_sorted_of_col and the heap's in-order walk agree");
 
 // The float the reference's loop holds for the dyadic node K / 2^LU of [beta0, 1]
 BIS_HD double bis_node_beta(long long K, int LU, double beta0) {

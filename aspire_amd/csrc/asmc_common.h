@@ -84,7 +84,7 @@ struct asmc_ctx {
     // device scratch (all allocated in asmc_ctx_create)
     double* d_partials;            // [ASMC_MAX_BLOCKS * ASMC_MAX_BETAS * 2] block partial sums
     double* d_small;               // [DS_LEN] small result vectors and state records (regions: asmc_scratch.h)
-    unsigned long long* d_keys;    // [ASMC_MAX_BETAS + 8] atomicMax keys + integer counters
+    unsigned long long* d_keys;    // [KEYS_LEN] atomicMax keys + integer counters (asmc_scratch.h)
     double* d_tiles;               // [scratch_tiles_len] scan tile aggregates (asmc_scratch.h)
     long long* d_tiles_i;          // [scratch_tiles_i_len] integer tile records (exact cdf: info + split; compaction)
     double* d_gram;                // [gram_blocks * d_max * d_max] gram partials
@@ -100,7 +100,7 @@ struct asmc_ctx {
     double* d_rec;                 // [4 * n_max] (ll, lp, lq, 0) records of asmc_gather's source population
     const void* rec_src[3];        // the arrays asmc_importance_step packed into d_rec (k_is_weights writes the records on
     int64_t rec_n;                 //   its way); rec_n != 0: still valid - the next asmc_gather of exactly these skips its packing pass
-    unsigned count_gen;            // k_count_nonfinite's count slots are used in turn (asmc_weights.hip)
+    unsigned count_gen;            // k_count_nonfinite's count slots are used in turn (asmc_weights.hip; COUNT_CELLS)
     uint64_t rec_token;            // generation of d_rec's contents (every pass that writes d_rec bumps it) ...
     const void* rec_hold_src[3];   // ... and the arrays / count / generation of a pack that asmc_normalized_weights_shard did on its
     int64_t rec_hold_n;            //   way: asmc_rec_claim(token) re-validates it for the next asmc_gather when nothing has
@@ -123,7 +123,7 @@ struct asmc_ctx {
     double* d_nuts_ws;             // U-turn checkpoints of the fused NUTS kernel, one slab per block (grown on demand)
     size_t nuts_ws_bytes;
     unsigned int* d_tilectr;       // [2 * ASMC_MAX_PCN_STEPS + 2] fused flow-proposal step: tile hand-out counters, blocks-done counters (one each per step), non-finite density count (64-bit)
-    unsigned int* d_bar;           // [1024 * 17] arrival counters + the poison cell of the persistent importance-weight kernel's grid barriers (4 KB apart; they only grow)
+    unsigned int* d_bar;           // [BAR_LEN] arrival counters + the poison cell of the persistent importance-weight kernel's grid barriers (4 KB apart; they only grow), the shard ticket, the count slots (asmc_scratch.h)
     unsigned int bar_base[17];     // their values when the next launch starts (top, groups)
     unsigned long long flow_nonfinite;  // non-finite flow densities among the proposals of the last asmc_pcn_mutate_flow
     int poison_lds;                // ASMC_POISON_LDS: a kernel that fills the LDS of every CU with NaN patterns runs in front of EVERY launch
@@ -223,7 +223,11 @@ int asmc_ref_factor_launch(asmc_ctx* ctx, int d, const double* sum, const double
 int asmc_gram_mm_launch(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x, const double* d_center, int* grid_out,
                         hipStream_t st, double* out2, double n_div);
 bool asmc_gram_mm_supported(int d, const void* x);
-// asmc_weights.hip: the persistent weight kernel of asmc_importance_step (results in the first 48 doubles of DS_BISECT)
+// asmc_weights.hip: k_weights_max for K candidates on the stream - keys in ctx->d_keys[0..K), NaN census in d_keys[KEYS_NAN]; the
+// memset in front of it zeroes all of d_keys, the search's ticket included (asmc_find_beta, asmc_find_beta_shard_reduce)
+int asmc_weights_max_launch(asmc_ctx* ctx, int64_t n, const double* ll, const double* lp, const double* lq, double beta0,
+                            const double* betas, int K, hipStream_t st);
+// asmc_is_weights.hip: the persistent weight kernel of asmc_importance_step (results in the first 48 doubles of DS_BISECT)
 int asmc_is_weights_launch(asmc_ctx* ctx, int64_t n, const double* ll, const double* lp, const double* lq, double beta0,
                            double target_eff, double tol, double* w, double* tiles, double* rec, hipStream_t st);
 // asmc_cdf.hip: the passes of the exact cdf of w [n] on the stream.
@@ -284,4 +288,19 @@ static inline int grid_for(int64_t n, int per_block, int cap) {
     if (g < 1) g = 1;
     if (g > cap) g = cap;
     return (int)g;
+}
+// grid of the weight files' grid-stride reduction kernels over n particles and kt candidate columns
+static inline int reduce_grid(const asmc_ctx* ctx, int64_t n, int kt) {
+    // enough work per thread to amortise the K-way block reduction; cap by scratch size
+    int per_block = ASMC_BLOCK * (kt >= 16 ? 4 : 8);
+    int cap = ctx->num_cu * 4;
+    if (cap > ASMC_MAX_BLOCKS) cap = ASMC_MAX_BLOCKS;
+    return grid_for(n, per_block, cap);
+}
+// argument check shared by the exported calls of the weight files (asmc_weights.hip, asmc_search.hip)
+static inline int check_common(asmc_ctx* ctx, int64_t n, const void* a, const void* b, const void* c) {
+    ASMC_REQUIRE(ctx != nullptr, "null ctx");
+    ASMC_REQUIRE(n > 0 && n <= ctx->n_max, "n out of range for this ctx");
+    ASMC_REQUIRE(a && b && c, "null device pointer");
+    return ASMC_OK;
 }

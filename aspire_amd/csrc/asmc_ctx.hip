@@ -187,7 +187,7 @@ int asmc_ctx_create(asmc_ctx** ctx_out, int device, int64_t n_max, int d_max) {
     };
     dmalloc((void**)&c->d_partials, sizeof(double) * ASMC_MAX_BLOCKS * ASMC_MAX_BETAS * 2);
     dmalloc((void**)&c->d_small, sizeof(double) * DS_LEN);
-    dmalloc((void**)&c->d_keys, sizeof(unsigned long long) * (ASMC_MAX_BETAS + 8));
+    dmalloc((void**)&c->d_keys, sizeof(unsigned long long) * KEYS_LEN);
     dmalloc((void**)&c->d_tiles, sizeof(double) * scratch_tiles_len(c->n_tiles_max));
     dmalloc((void**)&c->d_tiles_i, sizeof(long long) * scratch_tiles_i_len(c->n_tiles_max));
     c->gram_cap = (size_t)c->gram_blocks * d_max * d_max;
@@ -214,8 +214,8 @@ int asmc_ctx_create(asmc_ctx** ctx_out, int device, int64_t n_max, int d_max) {
     dmalloc((void**)&c->d_mh, sizeof(unsigned long long) * ASMC_MAX_PCN_STEPS);
     dmalloc((void**)&c->d_nuts, sizeof(unsigned long long) * (4 * ASMC_MAX_PCN_STEPS + 8));
     if (e == hipSuccess) e = hipMemset(c->d_tilectr, 0, ASMC_TILECTR_BYTES);
-    dmalloc((void**)&c->d_bar, sizeof(unsigned int) * 1024 * 17);
-    if (e == hipSuccess) e = hipMemset(c->d_bar, 0, sizeof(unsigned int) * 1024 * 17);
+    dmalloc((void**)&c->d_bar, sizeof(unsigned int) * BAR_LEN);
+    if (e == hipSuccess) e = hipMemset(c->d_bar, 0, sizeof(unsigned int) * BAR_LEN);
     dmalloc((void**)&c->d_pcgtab, sizeof(unsigned long long) * (64 * 4 + 8));
     dmalloc((void**)&c->d_select, sizeof(long long) * (2 * (ASMC_SELECT_THREADS / 64) + 8));
     dmalloc((void**)&c->d_ptab, sizeof(double) * (2 * 32 * 32 + 32 + 3 * ASMC_MAX_COMPONENTS * (1 + 2 * 32) + 64));

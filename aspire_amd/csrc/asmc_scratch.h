@@ -1,5 +1,6 @@
-// asmc_scratch.h — the one map of the context's shared scratch: ctx->d_small, ctx->h_pinned, ctx->d_tiles, ctx->d_tiles_i.
-// Included by asmc_common.h behind struct asmc_ctx; no other file adds a number to one of these four pointers.
+// asmc_scratch.h — the one map of the context's shared scratch: ctx->d_small, ctx->h_pinned, ctx->d_tiles, ctx->d_tiles_i,
+// ctx->d_flags, ctx->d_bar and the tail of ctx->d_keys.
+// Included by asmc_common.h behind struct asmc_ctx; no other file adds a number to one of these pointers.
 //
 // Every region has an offset and a length in elements of its buffer, an owner (the file whose calls write it) and a
 // lifetime class:
@@ -23,7 +24,7 @@ constexpr int DS_REF_STATUS = 2300;      // TRANSIENT  asmc_moments.hip, asmc_st
                                          //            pinned cell by the same call
 constexpr int DS_STUDENT_EM = 2320;      // TRANSIENT  asmc_student.hip: the EM's scalars
 constexpr int DS_STUDENT_EM_LEN = 8;
-constexpr int DS_BISECT = 2560;          // HELD       asmc_weights.hip: state record of the beta search (k_bis_sums,
+constexpr int DS_BISECT = 2560;          // HELD       asmc_search.hip, asmc_is_weights.hip: state record of the beta search (k_bis_sums,
 constexpr int DS_BISECT_REC = 64;        //            k_is_weights) until the result call copies it out; the folded sharded
 constexpr int DS_BISECT_LEN = 2 * DS_BISECT_REC;  //    search alternates between two records (round r in record r & 1)
 constexpr int DS_TRTAB = 3072;           // TRANSIENT  asmc_pcn.hip: packed table of the transform epilogue (k_trtab_pack)
@@ -51,7 +52,7 @@ constexpr int HP_GRAM_CENTER = 2048;     // TRANSIENT  asmc_moments.hip: staging
 constexpr int HP_GRAM_CENTER_LEN = 128;
 constexpr int HP_PCG_TAB = 4096;         // TRANSIENT  asmc_resample.hip: staging of the PCG64 jump table (u64), rebuilt when the
 constexpr int HP_PCG_TAB_LEN = 256;      //            generator's increment changes
-constexpr int HP_STEP_RESULT = 4096 + 512;  // HELD    asmc_weights.hip: the importance step's result record, from
+constexpr int HP_STEP_RESULT = 4096 + 512;  // HELD    asmc_is_weights.hip: the importance step's result record, from
 constexpr int HP_STEP_RESULT_LEN = 40 + 4 * 64;  //    asmc_importance_result_enqueue to asmc_importance_result (search state
                                          //            [64], poison word); asmc_find_beta, asmc_find_beta_shard_result and
                                          //            asmc_shard_step_result (40 + 4 world doubles) fill and read it in one call
@@ -90,6 +91,38 @@ constexpr size_t scratch_flags_moved_off(int64_t n) { return scratch_flags_fill(
 constexpr bool scratch_flags_fit(int64_t n) { return scratch_flags_moved_off(n) + scratch_flags_fill(n) <= scratch_flags_len(n); }
 static_assert(scratch_flags_fit(1) && scratch_flags_fit(63) && scratch_flags_fit(193) && scratch_flags_fit(1 << 20) && scratch_flags_fit((1 << 20) + 1),
               "parities and moved marks, each rounded to 16 bytes, stay inside the allocation");
+
+// ---- ctx->d_bar: 32-bit words on the device, zeroed at creation ----------------------------------------------------------------
+// The grid barrier of the persistent importance-weight kernel (asmc_is_weights.hip) and, behind its cells, three self-resetting
+// counters of other kernels.  asmc_importance_result zeroes words [0, BAR_ISW_RESET_LEN) after a barrier time-out: that range must
+// end in front of the cells of the other owners (checked below).
+constexpr int BAR_LEN = 1024 * 17;
+constexpr int ISW_GROUPS = 8;            //            arrival groups of the barrier (isw_barrier)
+constexpr int ISW_BAR_STRIDE = 1024;     //            its counters lie 4 KB apart (different memory channels)
+constexpr int BAR_ISW_TOP = 0;           // HELD       asmc_is_weights.hip: top counter; group g counts in word ISW_BAR_STRIDE * (1 + g).
+                                         //            They only grow: held from launch to launch (ctx->bar_base[] mirrors them)
+constexpr int ISW_POISON_CELL = ISW_BAR_STRIDE * (ISW_GROUPS + 2);  // HELD  asmc_is_weights.hip: raised by a barrier that timed out,
+                                         //            until asmc_importance_result reads it and resets the range below
+constexpr int BAR_ISW_RESET_LEN = ISW_BAR_STRIDE * (ISW_GROUPS + 3);  //  words that reset covers
+constexpr int SHARD_TICKET_CELL = 1024 * 12;  // TRANSIENT  asmc_search.hip: arrival counter of k_weights_m2_lse_shard (the last
+                                         //            block zeroes it again)
+constexpr int COUNT_CELLS = 1024 * 12 + 64;  // HELD   asmc_weights.hip: two {NaN, inf} count slots of k_count_nonfinite (u64 each), used in
+constexpr int COUNT_CELLS_LEN = 8;       //            turn, from asmc_count_nonfinite_enqueue to the read-back of asmc_count_slot
+static_assert(BAR_ISW_TOP + ISW_BAR_STRIDE * (1 + ISW_GROUPS) <= ISW_POISON_CELL && ISW_POISON_CELL < BAR_ISW_RESET_LEN,
+              "the barrier's counters and the poison cell lie inside the range a time-out resets");
+static_assert(BAR_ISW_RESET_LEN <= SHARD_TICKET_CELL && BAR_ISW_RESET_LEN <= COUNT_CELLS,
+              "the reset after a barrier time-out ends in front of the shard ticket and the count slots");
+static_assert(SHARD_TICKET_CELL < COUNT_CELLS && COUNT_CELLS + COUNT_CELLS_LEN <= BAR_LEN, "every cell of d_bar lies inside its allocation");
+static_assert(COUNT_CELLS % 2 == 0, "the count slots are 8-byte cells in an array of 4-byte words");
+static_assert(sizeof(asmc_ctx::bar_base) / sizeof(unsigned int) >= 1 + ISW_GROUPS, "ctx->bar_base[] mirrors the top counter and every group");
+
+// ---- ctx->d_keys: 64-bit words on the device; [0, ASMC_MAX_BETAS) atomicMax keys, one per candidate (k_weights_max), then ----------
+constexpr int KEYS_LEN = ASMC_MAX_BETAS + 8;
+constexpr int KEYS_NAN = ASMC_MAX_BETAS;         // HELD  asmc_weights.hip: NaN log-weights the last k_weights_max counted, until the
+                                                 //       search that enqueued it has read it (k_bis_sums' record, asmc_find_beta)
+constexpr int KEYS_SEARCH_TICKET = ASMC_MAX_BETAS + 4;  // HELD  asmc_search.hip: arrival counter of k_bis_sums (its low 32 bits), over
+                                                 //       the rounds of one search; the max pass's memset zeroes the whole array
+static_assert(KEYS_NAN < KEYS_SEARCH_TICKET && KEYS_SEARCH_TICKET < KEYS_LEN, "the key tail lies inside its allocation");
 
 // ---- the checks ------------------------------------------------------------------------------------------------------------
 struct ScratchRegion {

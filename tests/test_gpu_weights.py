@@ -1,4 +1,4 @@
-"""The weight, ESS and temperature-search kernels of csrc/asmc_weights.hip on every dispatch path and at the edges, against the
+"""The weight, ESS and temperature-search kernels of csrc/asmc_weights.hip, asmc_search.hip and asmc_is_weights.hip on every dispatch path and at the edges, against the
 long-double restatement of tests/weights_ref.py (tolerance formulas: its docstring and DESIGN.md section 3.16; none comes from the
 device's output).
 
@@ -729,9 +729,10 @@ def test_sharded_search_moments_and_weights(ranks, cu, world, layout, kind, fold
 
 # ---- every kernel of the file ran -----------------------------------------------------------------------------------------------------------
 def test_every_kernel_symbol_ran():
-    """Closes the module: every __global__ kernel defined in csrc/asmc_weights.hip, in every instantiation the library
-    launches, appears in an asserted launch above.  It needs the whole module to have run: under a -k selection it fails."""
-    src = open(os.path.join(ROOT, "aspire_amd", "csrc", "asmc_weights.hip")).read()
+    """Closes the module: every __global__ kernel defined in csrc/asmc_weights.hip, asmc_search.hip and asmc_is_weights.hip, in every
+    instantiation the library launches, appears in an asserted launch above.  It needs the whole module to have run: under a -k
+    selection it fails."""
+    src = "".join(open(os.path.join(ROOT, "aspire_amd", "csrc", f)).read() for f in ("asmc_weights.hip", "asmc_search.hip", "asmc_is_weights.hip"))
     kernels = set(re.findall(r"__global__\s+__launch_bounds__\([A-Z_0-9a-z]+\)\s+void\s+(k_[a-z0-9_]+)\s*\(", src))
     assert len(kernels) == 12, sorted(kernels)
     templated = {"k_weights_max": [f"Li{k}" for k in (1, 2, 4, 8, 16, 32)], "k_weights_sums": [f"Li{k}" for k in (1, 2, 4, 8, 16, 32)],

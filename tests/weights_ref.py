@@ -1,5 +1,5 @@
 """Host restatement of the tempered log-weights, their log-sum-exp reductions, ESS, the evidence moments, the normalised weights
-and the adaptive-temperature search (csrc/asmc_weights.hip, csrc/asmc_bisect.h), in numpy fp64 and numpy long double.
+and the adaptive-temperature search (csrc/asmc_weights.hip, csrc/asmc_search.hip, csrc/asmc_is_weights.hip, csrc/asmc_bisect.h), in numpy fp64 and numpy long double.
 
 What is restated (reference paths relative to its root; no program text taken from it): samples.py:1221-1249 and :1276-1277 (the
 log-weights, the evidence ratio and its variance, the normalised weights), utils.py:248-255 (log-sum-exp: maximum, then the sum of
@@ -67,7 +67,7 @@ ISW_CHUNK = 4096
 MAX_BLOCKS = 2048
 
 
-# ---- dispatch geometry (csrc/asmc_weights.hip reduce_grid, grid_for) -------------------------------------------------------------
+# ---- dispatch geometry (csrc/asmc_common.h reduce_grid, grid_for) -------------------------------------------------------------
 def bucket_of(K):
     kt = 1
     while kt < K:
