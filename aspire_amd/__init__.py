@@ -6,11 +6,11 @@ The package holds only what that hot path needs: the HIP kernels + C ABI (`csrc/
 reference's operator interface (`samples`, `samplers`, `aspire`, `flows`, `targets`).
 """
 from .aspire import Aspire
-from .flows import CouplingFlow, Flow, GaussianFlow
+from .flows import CouplingFlow, Flow, GaussianFlow, NSFFlow
 from .history import SMCHistory
 from .samples import MCMCSamples, PTMCMCSamples, Samples, SMCSamples
 from .targets import DiagGaussianMixture
 
 __all__ = ["Aspire", "Samples", "SMCSamples", "MCMCSamples", "PTMCMCSamples", "SMCHistory", "Flow", "GaussianFlow", "CouplingFlow",
-           "DiagGaussianMixture"]
+           "NSFFlow", "DiagGaussianMixture"]
 __version__ = "0.1.0"

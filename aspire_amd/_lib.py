@@ -26,8 +26,8 @@ COUNT_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 ASMC_BIS_REC = 40
 ASMC_SELECT_THREADS = 262144
 ASMC_STUDENT_MAX_ROWS = 16384
-ASMC_ABI_VERSION = 31
-ASMC_FLOW_COUPLING, ASMC_FLOW_MAF = 0, 1  # asmc_coupling.kind
+ASMC_ABI_VERSION = 32
+ASMC_FLOW_COUPLING, ASMC_FLOW_MAF, ASMC_FLOW_NSF = 0, 1, 2  # asmc_coupling.kind
 ASMC_MAX_COUNT_CELLS = 64  # asmc_pcn_set_count_cells
 ASMC_CDF_REC = 9
 ASMC_CDF_STATE = 36
@@ -106,13 +106,13 @@ class AsmcCoupling(ctypes.Structure):
         ("dims", c_int32),
         ("n_layers", c_int32),
         ("hidden", c_int32),
-        ("kind", c_int32),  # ASMC_FLOW_COUPLING / ASMC_FLOW_MAF
+        ("kind", c_int32),  # ASMC_FLOW_COUPLING / ASMC_FLOW_MAF / ASMC_FLOW_NSF
         ("packed_dev", c_void_p),
         ("loc_dev", c_void_p),
         ("scale_dev", c_void_p),
         ("log_scale_sum", c_double),
         ("affine", c_int32),  # ASMC_AFFINE_TANH (0) / ASMC_AFFINE_SOFTCLIP (1)
-        ("reserved", c_int32),
+        ("reserved", c_int32),  # ASMC_FLOW_NSF: the spline's bin count; 0 otherwise
     ]
 
 
@@ -242,6 +242,8 @@ SIGNATURES = {
     "asmc_coupling_pack": (_i, [_i, _i, _i, POINTER(c_void_p), POINTER(c_void_p), _vp]),
     "asmc_maf_pack_floats": (_i64, [_i, _i, _i]),
     "asmc_maf_pack": (_i, [_i, _i, _i, POINTER(c_void_p), POINTER(c_void_p), _vp]),
+    "asmc_nsf_pack_floats": (_i64, [_i, _i, _i, _i]),
+    "asmc_nsf_pack": (_i, [_i, _i, _i, _i, POINTER(c_void_p), POINTER(c_void_p), _vp]),
     "asmc_coupling_logprob": (_i, [_vp, _i64, _i, _vp, POINTER(AsmcCoupling), _vp, _vp]),
     "asmc_coupling_sample": (_i, [_vp, _i64, _i, POINTER(AsmcCoupling), _u64, _u64, _u32, _vp, _vp, _vp]),
     "asmc_transform_forward": (_i, [_vp, _i64, _i, _vp, _vp, _vp, POINTER(AsmcTransform), _vp]),

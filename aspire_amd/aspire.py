@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from ._xp import is_torch_namespace, to_numpy
-from .flows import CouplingFlow, Flow, GaussianFlow, MAFFlow
+from .flows import CouplingFlow, Flow, GaussianFlow, MAFFlow, NSFFlow
 from .history import FlowHistory, History
 from .samples import Samples
 from .samplers.base import IdentityTransform, Sampler
@@ -86,7 +86,8 @@ class Aspire:
 
     def init_flow(self):
         """aspire.py:177-206.  Backends: "coupling" (PyTorch RealNVP, HIP kernels in the hot path), "maf" (masked autoregressive
-        flow, the reference's default flow class; PyTorch passes only) and "gaussian" (analytic, HIP).
+        flow, the reference's default flow class; PyTorch passes only), "nsf" (neural spline flow, HIP kernels in the hot path) and
+        "gaussian" (analytic, HIP).
         "zuko" is accepted when zuko is importable and otherwise maps to "coupling" with a warning
         (zuko is not part of this image)."""
         backend = self.flow_backend.lower()
@@ -107,13 +108,26 @@ class Aspire:
         if backend == "zuko":
             # the reference's default backend (aspire.py:79-98) with its default flow class, a masked autoregressive flow
             # (flows/torch/flows.py:140-164).  zuko itself is absent: `MAFFlow` restates the architecture and runs on the HIP kernels.
-            # Other zuko classes (NSF, ...) have no counterpart: the coupling flow stands in, with a warning.
+            # Other zuko classes (NSF, ...) keep the coupling stand-in, with a warning (a spline flow: flow_backend="nsf").
             fc = str(self.flow_kwargs.get("flow_class", "MAF")).upper()
             if fc != "MAF":
-                logger.warning("zuko flow class %r is not available here; using the built-in coupling flow", fc)
+                logger.warning("zuko flow class %r is not available here; using the built-in coupling flow%s", fc,
+                               ' (flow_backend="nsf" builds the neural spline flow)' if fc == "NSF" else "")
                 self.flow_kwargs = {k: v for k, v in self.flow_kwargs.items() if k != "flow_class"}
             backend = "maf" if fc == "MAF" else "coupling"
-        if backend == "maf" or str(self.flow_kwargs.get("flow_class", "")).upper() == "MAF":
+        if backend == "nsf":
+            # zuko's NSF (examples/smc_example.py:82): masked autoregressive rational-quadratic spline transforms on the HIP kernels
+            kw = {k: v for k, v in self.flow_kwargs.items() if k != "flow_class"}
+            if "transforms" in kw:  # zuko's name for the number of autoregressive transforms
+                kw["n_transforms"] = int(kw.pop("transforms"))
+            known = {"n_transforms", "hidden_features", "bins", "seed", "flow_dtype"}
+            unknown = sorted(k for k in kw if k not in known)
+            if unknown:  # zuko-only options (passes, randperm, activation, ...)
+                logger.warning("NSFFlow ignores flow_kwargs %s (zuko options without a counterpart here)", unknown)
+                kw = {k: v for k, v in kw.items() if k in known}
+            self._flow = NSFFlow(dims=self.dims, device=self.device or "cpu", data_transform=data_transform,
+                                 dtype=kw.pop("flow_dtype", torch.float32), **kw)
+        elif backend == "maf" or str(self.flow_kwargs.get("flow_class", "")).upper() == "MAF":
             # the reference's default flow class (ZukoFlow(flow_class="MAF"), flows/torch/flows.py:140-164): PyTorch passes only
             kw = {k: v for k, v in self.flow_kwargs.items() if k != "flow_class"}
             if "transforms" in kw:  # zuko's name for the number of autoregressive transforms
@@ -296,7 +310,7 @@ class Aspire:
         fc = str(self.flow_kwargs.get("flow_class", "MAF")).upper()
         if backend == "gaussian":
             raise ValueError("the analytic Gaussian proposal has no parameters to load")
-        cls = MAFFlow if (backend == "maf" or (backend == "zuko" and fc == "MAF") or fc == "MAF" and backend != "coupling") else CouplingFlow
+        cls = NSFFlow if backend == "nsf" else MAFFlow if (backend == "maf" or (backend == "zuko" and fc == "MAF") or fc == "MAF" and backend != "coupling") else CouplingFlow
         self._flow = cls.load(h5_file, path=path, device=self.device or "cpu")
 
     def get_sampler_class(self, sampler_type: str) -> Callable:

@@ -216,6 +216,10 @@ int asmc_flow16_sample(asmc_ctx* ctx, int64_t n, int x_dtype, const asmc_couplin
                        uint32_t draw_id, void* x_out, double* lq_out, hipStream_t st);
 bool asmc_pcn_flow16_ok(const asmc_pcn_params* prm, const asmc_coupling* f);
 bool asmc_flow_math_split();
+// asmc_nsf.hip: neural spline flows (packed layout 2: 16-particle groups, parameter-major output blocks, streamed weights)
+int asmc_nsf_logprob(asmc_ctx* ctx, int64_t n, int x_dtype, const void* x, const asmc_coupling* f, double* out, hipStream_t st);
+int asmc_nsf_sample(asmc_ctx* ctx, int64_t n, int x_dtype, const asmc_coupling* f, unsigned long long seed, unsigned long long gid0,
+                    uint32_t draw_id, void* x_out, double* lq_out, hipStream_t st);
 
 // k_ref_factor on the stream (asmc_moments.hip; asmc_reference_factor and the Student-t EM of asmc_student.hip)
 int asmc_ref_factor_launch(asmc_ctx* ctx, int d, const double* sum, const double* gram, double n_mean, double denom, double* out,

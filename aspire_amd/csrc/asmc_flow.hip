@@ -676,9 +676,10 @@ extern "C" int asmc_coupling_logprob(asmc_ctx* ctx, int64_t n, int x_dtype, cons
     ASMC_REQUIRE(flow && x_dev && out_dev, "null pointer");
     ASMC_REQUIRE(n > 0, "n must be positive");
     ASMC_REQUIRE(flow->packed_dev && flow->loc_dev && flow->scale_dev, "flow parameters missing");
-    ASMC_REQUIRE(flow->kind == ASMC_FLOW_COUPLING || flow->kind == ASMC_FLOW_MAF, "bad flow kind");
+    ASMC_REQUIRE(flow->kind == ASMC_FLOW_COUPLING || flow->kind == ASMC_FLOW_MAF || flow->kind == ASMC_FLOW_NSF, "bad flow kind");
     ASMC_REQUIRE(flow->affine == ASMC_AFFINE_TANH || (flow->affine == ASMC_AFFINE_SOFTCLIP && flow->kind == ASMC_FLOW_MAF), "bad affine form (the soft-clipped form is for autoregressive flows)");
     hipStream_t st = (hipStream_t)stream;
+    if (flow->kind == ASMC_FLOW_NSF) return asmc_nsf_logprob(ctx, n, x_dtype, x_dev, flow, out_dev, st);
     if (asmc_flow_layout(flow->kind, flow->dims, flow->hidden) == 1) {
         ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
         ASMC_REQUIRE(flow->n_layers >= 1, "bad n_layers");
@@ -733,8 +734,10 @@ extern "C" int asmc_coupling_sample(asmc_ctx* ctx, int64_t n, int x_dtype, const
     ASMC_REQUIRE(n > 0, "n must be positive");
     ASMC_REQUIRE(flow->packed_dev && flow->loc_dev && flow->scale_dev, "flow parameters missing");
     ASMC_REQUIRE(x_dtype == ASMC_F64 || x_dtype == ASMC_F32, "bad x_dtype");
-    ASMC_REQUIRE(flow->kind == ASMC_FLOW_COUPLING || flow->kind == ASMC_FLOW_MAF, "bad flow kind");
+    ASMC_REQUIRE(flow->kind == ASMC_FLOW_COUPLING || flow->kind == ASMC_FLOW_MAF || flow->kind == ASMC_FLOW_NSF, "bad flow kind");
     ASMC_REQUIRE(flow->affine == ASMC_AFFINE_TANH || (flow->affine == ASMC_AFFINE_SOFTCLIP && flow->kind == ASMC_FLOW_MAF), "bad affine form (the soft-clipped form is for autoregressive flows)");
+    if (flow->kind == ASMC_FLOW_NSF)
+        return asmc_nsf_sample(ctx, n, x_dtype, flow, seed, gid0, draw_id, x_out_dev, lq_out_dev, (hipStream_t)stream);
     if (asmc_flow_layout(flow->kind, flow->dims, flow->hidden) == 1)
         return asmc_flow16_sample(ctx, n, x_dtype, flow, seed, gid0, draw_id, x_out_dev, lq_out_dev, (hipStream_t)stream);
     if (flow->kind == ASMC_FLOW_MAF) {

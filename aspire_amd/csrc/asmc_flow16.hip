@@ -37,6 +37,8 @@ extern "C" int asmc_flow_layout(int kind, int dims, int hidden) {
         // zero-padded to D = 64 (density, sampling and the one-kernel step).
         return (dims > 32 || hidden == 128) ? 1 : 0;
     }
+    if (kind == ASMC_FLOW_NSF)  // layout 2 (asmc_nsf.hip): 16-particle groups, parameter-major output blocks, every matrix streamed
+        return (dims >= 1 && dims <= 32 && hidden != 128) ? 2 : -1;
     return -1;
 }
 
@@ -569,6 +571,7 @@ static size_t f16_step_lds(int n_layers, int c_ll, int c_lp, int noise) {
 
 // whether the one-kernel step takes this mutation (prm->d is the PADDED dimension 64 / 128; the flow keeps its own dims)
 bool asmc_pcn_flow16_ok(const asmc_pcn_params* prm, const asmc_coupling* f) {
+    if (f->kind != ASMC_FLOW_COUPLING && f->kind != ASMC_FLOW_MAF) return false;
     if (getenv("ASMC_FLOW_SPLIT") || getenv("ASMC_FLOW16_OFF") || !asmc_flow_math_split()) return false;
     if (!(prm->d == 64 || prm->d == 128) || asmc_flow_layout(f->kind, f->dims, f->hidden) != 1 || f16_pad_dim(f->dims) != prm->d) return false;
     const int cl = prm->log_likelihood.n_components, cp = prm->log_prior.n_components;

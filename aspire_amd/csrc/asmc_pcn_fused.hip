@@ -1265,6 +1265,7 @@ static int launch_pcn_flow_fused(asmc_ctx* ctx, int64_t n, double* ll, double* l
 // every coupling layer resident in LDS next to nothing else
 bool asmc_pcn_flow_fused_ok(const asmc_pcn_params* prm, const asmc_coupling* f) {
     if (getenv("ASMC_FLOW_SPLIT")) return false;
+    if (f->kind != ASMC_FLOW_COUPLING && f->kind != ASMC_FLOW_MAF) return false;  // (a spline flow: the un-fused step loop around asmc_coupling_logprob)
     // d = 32 as it is; fewer dimensions zero-padded to 32 by asmc_pcn_mutate_flow (prm->d is 32 by then, the flow keeps its own)
     if (prm->d != 32 || f->dims > 32 || f->dims < 2) return false;
     if (f->dims != 32 && !(FUSED_MVMFMA && FUSED_INPLACE)) return false;  // (the padded layout lives in the matrix-core variant's tables)
@@ -1355,6 +1356,7 @@ bool asmc_pcn_flow_fused_beta1_ok(const asmc_coupling* f, int img_words) {
     const char* mode = getenv("ASMC_FLOW_BETA1");
     if (mode && !strcmp(mode, "full")) return false;
     if (img_words <= 0 || !asmc_flow_math_split()) return false;
+    if (f->kind != ASMC_FLOW_COUPLING && f->kind != ASMC_FLOW_MAF) return false;
 #ifdef FUSED_ONLY_HEADLINE
     return f->kind == ASMC_FLOW_COUPLING && f->hidden == 64;
 #else

@@ -65,12 +65,13 @@ class DeviceCoupling:
     loc: torch.Tensor  # fp32 [dims]
     scale: torch.Tensor  # fp32 [dims]
     log_scale_sum: float
-    kind: int = 0  # ASMC_FLOW_COUPLING (0) / ASMC_FLOW_MAF (1)
+    kind: int = 0  # ASMC_FLOW_COUPLING (0) / ASMC_FLOW_MAF (1) / ASMC_FLOW_NSF (2)
     affine: int = 0  # ASMC_AFFINE_TANH (0) / ASMC_AFFINE_SOFTCLIP (1: zuko's monotonic affine form, autoregressive flows only)
+    bins: int = 0  # ASMC_FLOW_NSF: bins of the spline (the struct's `reserved` word); 0 for the affine kinds
 
     def c_struct(self) -> AsmcCoupling:
         return AsmcCoupling(self.dims, self.n_layers, self.hidden, self.kind, self.packed.data_ptr(), self.loc.data_ptr(),
-                            self.scale.data_ptr(), self.log_scale_sum, self.affine, 0)
+                            self.scale.data_ptr(), self.log_scale_sum, self.affine, self.bins)
 
 
 @dataclass
@@ -139,6 +140,27 @@ def pack_coupling(lib, dims: int, hidden: int, weights, biases) -> np.ndarray:
     wp = (ctypes.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
     bp = (ctypes.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
     check(lib.asmc_coupling_pack(dims, n_layers, hidden, wp, bp, out.ctypes.data_as(ctypes.c_void_p)), "asmc_coupling_pack")
+    return out
+
+
+def pack_nsf(lib, dims: int, hidden: int, bins: int, weights, biases) -> np.ndarray:
+    """Host-side packing of a neural spline flow (asmc_nsf_pack): the MASKED dense layers, three per transform, in
+    torch.nn.Linear layout ([hidden, dims], [hidden, hidden], [dims (3 bins - 1), hidden], output rows feature major)."""
+    n_tr = len(weights) // 3
+    assert len(weights) == len(biases) == 3 * n_tr and n_tr >= 1
+    ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
+    bs = [np.ascontiguousarray(b, dtype=np.float32) for b in biases]
+    rows = dims * (3 * bins - 1)
+    for c in range(n_tr):
+        assert ws[3 * c].shape == (hidden, dims) and ws[3 * c + 1].shape == (hidden, hidden) and ws[3 * c + 2].shape == (rows, hidden)
+        assert bs[3 * c].shape == (hidden,) and bs[3 * c + 1].shape == (hidden,) and bs[3 * c + 2].shape == (rows,)
+    nfl = lib.asmc_nsf_pack_floats(dims, n_tr, hidden, bins)
+    if nfl < 0:
+        raise _lib.AsmcError(f"spline flow shape not supported by the HIP kernel: {lib.asmc_last_error().decode()}")
+    out = np.empty(nfl, dtype=np.float32)
+    wp = (ctypes.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+    bp = (ctypes.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
+    check(lib.asmc_nsf_pack(dims, n_tr, hidden, bins, wp, bp, out.ctypes.data_as(ctypes.c_void_p)), "asmc_nsf_pack")
     return out
 
 
@@ -728,6 +750,15 @@ class HipEngine:
                               self.asarray(np.asarray(loc, dtype=np.float32), dtype=torch.float32),
                               self.asarray(scale, dtype=torch.float32), float(np.log(scale.astype(np.float64)).sum()),
                               kind=_lib.ASMC_FLOW_MAF, affine=int(affine))
+
+    def make_nsf(self, dims: int, hidden: int, bins: int, weights, biases, loc, scale) -> DeviceCoupling:
+        """A neural spline flow on the device (include/asmc.h ASMC_FLOW_NSF): `weights` are the MASKED matrices."""
+        packed = pack_nsf(self.lib, dims, hidden, bins, weights, biases)
+        scale = np.asarray(scale, dtype=np.float32)
+        return DeviceCoupling(dims, len(weights) // 3, hidden, self.asarray(packed, dtype=torch.float32),
+                              self.asarray(np.asarray(loc, dtype=np.float32), dtype=torch.float32),
+                              self.asarray(scale, dtype=torch.float32), float(np.log(scale.astype(np.float64)).sum()),
+                              kind=_lib.ASMC_FLOW_NSF, bins=int(bins))
 
     def coupling_logprob(self, x: torch.Tensor, flow: DeviceCoupling) -> torch.Tensor:
         assert x.is_contiguous() and x.dim() == 2 and x.shape[1] == flow.dims

@@ -734,3 +734,155 @@ class MAFFlow(CouplingFlow):
             self._packed = (key, engine.make_maf(self.dims, hidden, ws, bs, self.loc.detach().cpu().numpy(),
                                                  self.scale.detach().cpu().numpy(), affine=1 if self.affine == "zuko" else 0))
         return self._packed[1]
+
+
+class _SplineAutoregressive(torch.nn.Module):
+    """One masked autoregressive transform whose univariate map is a monotonic rational-quadratic spline (Durkan et al. 2019):
+    `bins` bins on [-bound, bound], the identity outside.  The MADE network d -> h -> h -> d (3 bins - 1) emits, per coordinate
+    i, rows i (3 bins - 1) + [0, bins) = widths, the next `bins` = heights, the last bins - 1 = interior derivatives (feature
+    major); all of them see only coordinates of strictly lower degree.  Same interface as `_Autoregressive`."""
+
+    def __init__(self, dims, hidden, reverse, bins=8, bound=5.0):
+        super().__init__()
+        deg_in = torch.arange(1, dims + 1)
+        if reverse:
+            deg_in = deg_in.flip(0)
+        self.register_buffer("order", deg_in)
+        layers, deg_prev = [], deg_in
+        for h in hidden:
+            deg_h = (torch.arange(h) % max(dims - 1, 1)) + 1
+            layers += [_MaskedLinear(len(deg_prev), h, (deg_h[:, None] >= deg_prev[None, :]).to(torch.get_default_dtype())),
+                       torch.nn.ReLU()]
+            deg_prev = deg_h
+        deg_out = deg_in.repeat_interleave(3 * bins - 1)
+        layers.append(_MaskedLinear(len(deg_prev), dims * (3 * bins - 1), (deg_out[:, None] > deg_prev[None, :]).to(torch.get_default_dtype())))
+        self.net = torch.nn.Sequential(*layers)
+        torch.nn.init.zeros_(self.net[-1].weight)  # the identity spline: an untrained flow is the standardised normal
+        torch.nn.init.zeros_(self.net[-1].bias)
+        self.dims, self.bins, self.bound = dims, int(bins), float(bound)
+
+    def _knots(self, raw):
+        cs = torch.cumsum(torch.softmax(raw, -1), -1)
+        inner = self.bound * (2.0 * cs[..., :-1] - 1.0)
+        lo = torch.full_like(inner[..., :1], -self.bound)
+        return torch.cat([lo, inner, -lo], -1)  # the last knot is +bound exactly
+
+    def _params(self, x):
+        K = self.bins
+        phi = self.net(x).reshape(x.shape[0], self.dims, 3 * K - 1)
+        w, h, dl = phi[..., :K], phi[..., K: 2 * K], phi[..., 2 * K:]
+        w = w / (1.0 + 2.0 * w.abs() / _LN_1000)
+        h = h / (1.0 + 2.0 * h.abs() / _LN_1000)
+        dl = dl / (1.0 + dl.abs() / _LN_1000)
+        one = torch.ones_like(dl[..., :1])
+        return self._knots(w), self._knots(h), torch.cat([one, torch.exp(dl), one], -1)
+
+    def _bin(self, knots, v):
+        k = (knots < v[..., None]).sum(-1) - 1
+        return (k >= 0) & (k < self.bins), k.clamp(0, self.bins - 1)
+
+    @staticmethod
+    def _at(t, k):
+        return t.gather(-1, k[..., None])[..., 0]
+
+    def forward(self, x):  # data -> latent
+        X, Y, D = self._params(x)
+        inside, k = self._bin(X, x)
+        x0, wd, y0, ht = self._at(X, k), self._at(X, k + 1) - self._at(X, k), self._at(Y, k), self._at(Y, k + 1) - self._at(Y, k)
+        d0, d1 = self._at(D, k), self._at(D, k + 1)
+        s = ht / wd
+        zeta = (x - x0) / wd
+        zz = zeta * (1.0 - zeta)
+        q = s + (d0 + d1 - 2.0 * s) * zz
+        y = y0 + ht * (s * zeta * zeta + d0 * zz) / q
+        lj = torch.log(s * s * (2.0 * s * zz + d0 * (1.0 - zeta) ** 2 + d1 * zeta * zeta) / (q * q))
+        return torch.where(inside, y, x), torch.where(inside, lj, torch.zeros_like(lj)).sum(-1)
+
+    def _invert(self, y, X, Y, D):
+        inside, k = self._bin(Y, y)
+        x0, wd, y0, ht = self._at(X, k), self._at(X, k + 1) - self._at(X, k), self._at(Y, k), self._at(Y, k + 1) - self._at(Y, k)
+        d0, d1 = self._at(D, k), self._at(D, k + 1)
+        s = ht / wd
+        eta = y - y0
+        t = d0 + d1 - 2.0 * s
+        a = ht * (s - d0) + eta * t
+        b = ht * d0 - eta * t
+        c2 = -s * eta
+        zeta = 2.0 * c2 / (-b - torch.sqrt(b * b - 4.0 * a * c2))
+        return torch.where(inside, x0 + zeta * wd, y)
+
+    def inverse(self, z):  # latent -> data: variable of degree 1 first
+        x = torch.zeros_like(z)
+        for k in torch.argsort(self.order).tolist():
+            X, Y, D = self._params(x)
+            x[:, k] = self._invert(z[:, k], X[:, k], Y[:, k], D[:, k])
+        _, lj = self.forward(x)
+        return x, -lj
+
+
+class NSFFlow(CouplingFlow):
+    """Neural spline flow (Durkan et al. 2019) - what the reference's SMC example asks zuko for (`flow_class="NSF"`,
+    examples/smc_example.py:82; `ZukoFlow` forwards any zuko class name, flows/torch/flows.py:155-164): `n_transforms` masked
+    autoregressive transforms with alternating variable order whose univariate map is a monotonic rational-quadratic spline of
+    `bins` bins on [-bound, bound] (`_SplineAutoregressive`).
+
+    **UNVERIFIED against zuko**: zuko is absent from the build image, so the spline is this repository's statement of zuko's
+    documented `MonotonicRQSTransform` (bound 5, slope 1e-3: widths and heights soft-clipped to |.| < ln(1000) / 2, derivatives
+    to |.| < ln(1000), softmax widths / heights, knot derivatives exp(.) with 1 at both ends) and of its feature-major output
+    rows (widths, heights, derivatives per coordinate); it is tested against an fp64 restatement of those formulas
+    (tests/nsf_ref.py), never against the package.
+
+    Training, `log_prob`, `log_prob_f64`, `forward` / `inverse`, save / load are CouplingFlow's PyTorch code.  In the hot path
+    the flow runs on the HIP kernels (`device_coupling` -> include/asmc.h ASMC_FLOW_NSF): `k_nsf_logprob` inside
+    `asmc_pcn_mutate_flow`'s step loop and `k_nsf_sample` for the proposal draw."""
+
+    def __init__(self, dims: int, n_transforms: int = 3, hidden_features=(64, 64), bins: int = 8, bound: float = 5.0,
+                 seed: int = 1234, device=None, dtype=torch.float32, data_transform=None):
+        Flow.__init__(self, dims, device=torch.device(device or "cpu"), data_transform=data_transform)
+        self.dtype = dtype
+        self._seed, self._rng_snapshot = int(seed), None
+        if int(bins) < 2 or not float(bound) > 0.0:
+            raise ValueError("NSFFlow needs bins >= 2 and bound > 0")
+        self.bins, self.bound = int(bins), float(bound)
+        hidden = tuple(map(int, hidden_features))
+        prev = torch.get_default_dtype()
+        torch.set_default_dtype(dtype)
+        try:
+            with self._private_rng():
+                self.layers = torch.nn.ModuleList([_SplineAutoregressive(dims, hidden, reverse=bool(i % 2), bins=self.bins, bound=self.bound)
+                                                   for i in range(n_transforms)])
+        finally:
+            torch.set_default_dtype(prev)
+        self.layers.to(device=self.device, dtype=dtype)
+        self.loc = torch.zeros(dims, device=self.device, dtype=dtype)
+        self.scale = torch.ones(dims, device=self.device, dtype=dtype)
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(seed)
+        self._packed, self._version = None, 0
+        self._init_args = dict(dims=int(dims), n_transforms=int(n_transforms), hidden_features=[int(h) for h in hidden],
+                               bins=self.bins, bound=self.bound, seed=int(seed), dtype=str(dtype).replace("torch.", ""))
+
+    def export_layers(self):
+        """(weights, biases): the MASKED fp32 matrices of the three dense layers of every transform, torch Linear layout
+        ([h, d], [h, h], [d (3 bins - 1), h], output rows feature major) - what `asmc_nsf_pack` takes."""
+        return MAFFlow.export_layers(self)
+
+    def device_coupling(self, engine):
+        """Pack the flow for the HIP kernels (asmc_coupling_logprob / _sample / asmc_pcn_mutate_flow with kind = ASMC_FLOW_NSF).
+        float32 flows of dims <= 32 with two equal hidden widths, 8 bins on [-5, 5] and no data transform; raises ValueError
+        otherwise so that callers fall back to the torch modules knowingly."""
+        if self.dtype != torch.float32:
+            raise ValueError("device_coupling needs a float32 flow")
+        if self._has_transform():
+            raise ValueError("the flow lives in the data transform's space; the kernel evaluates log q in x")
+        if self.bins != 8 or self.bound != 5.0 or self.dims > 32:
+            raise ValueError("the HIP spline kernels take bins = 8, bound = 5 and dims <= 32")
+        key = (id(engine), self._version)
+        if self._packed is None or self._packed[0] != key:
+            ws, bs = self.export_layers()
+            hidden = ws[0].shape[0]
+            if ws[1].shape != (hidden, hidden) or hidden not in (32, 64):
+                raise ValueError("the HIP spline kernels need two equal hidden widths of 32 or 64")
+            self._packed = (key, engine.make_nsf(self.dims, hidden, self.bins, ws, bs, self.loc.detach().cpu().numpy(),
+                                                 self.scale.detach().cpu().numpy()))
+        return self._packed[1]

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 31
+#define ASMC_ABI_VERSION 32
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -633,11 +633,12 @@ int asmc_pcn_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x_dev,
  *   asmc_coupling_logprob: out_dev[i] = log q(x_i). */
 #define ASMC_FLOW_COUPLING 0 /* affine coupling layers with alternating half masks (above) */
 #define ASMC_FLOW_MAF 1      /* masked autoregressive transforms (below) */
+#define ASMC_FLOW_NSF 2      /* masked autoregressive rational-quadratic spline transforms (ABI 32, below) */
 typedef struct asmc_coupling {
     int32_t dims;
     int32_t n_layers; /* coupling layers, or autoregressive transforms */
     int32_t hidden;
-    int32_t kind;     /* ASMC_FLOW_COUPLING / ASMC_FLOW_MAF: every entry point that takes a flow dispatches on it */
+    int32_t kind;     /* ASMC_FLOW_COUPLING / ASMC_FLOW_MAF / ASMC_FLOW_NSF: every entry point that takes a flow dispatches on it */
     const float* packed_dev; /* asmc_coupling_pack output copied to the device */
     const float* loc_dev;    /* [dims] */
     const float* scale_dev;  /* [dims] */
@@ -648,14 +649,15 @@ typedef struct asmc_coupling {
                                 (flows/torch/flows.py:156-168; aspire_amd.flows.MAFFlow.from_zuko_state_dict).  zuko is absent
                                 from the build image: that form follows its documented arithmetic and is UNVERIFIED against it.
                                 Autoregressive flows only. */
-    int32_t reserved;
+    int32_t reserved;        /* ASMC_FLOW_NSF (ABI 32): the spline's bin count (8); 0 for the other kinds */
 } asmc_coupling;
 #define ASMC_AFFINE_TANH 0
 #define ASMC_AFFINE_SOFTCLIP 1
 /* Packed layout of a flow of this shape: 0 = 32-particle tiles with every layer resident in LDS (dims <= 32), 1 = 16-particle
  * groups with the weights streamed through LDS (32 < dims <= 128: csrc/asmc_flow16.hip; coupling flows need even dims; and -
  * ABI 23 - autoregressive flows of hidden width 128 at ANY dims <= 128: the resident layout holds one such transform at most),
- * < 0 = no kernel.  The pack functions below choose it from the shape; every entry point that takes an asmc_coupling follows.
+ * 2 = a spline flow (ASMC_FLOW_NSF, dims <= 32, hidden 32 / 64: 16-particle groups, parameter-major output blocks, every matrix
+ * streamed: csrc/asmc_nsf.hip), < 0 = no kernel.  The pack functions below choose it from the shape; every entry point that takes an asmc_coupling follows.
  * The one-kernel mutation step (asmc_pcn_mutate_flow) exists for hidden widths 32 / 64 / 128 in layout 1 (ABI 23; width 64 only
  * before) and for 32 / 64 - coupling flows: 128 too, while the layers fit the LDS - in layout 0. */
 int asmc_flow_layout(int kind, int dims, int hidden);
@@ -692,6 +694,24 @@ int asmc_coupling_sample(asmc_ctx* ctx, int64_t n, int x_dtype, const asmc_coupl
 int64_t asmc_maf_pack_floats(int dims, int n_transforms, int hidden);
 int asmc_maf_pack(int dims, int n_transforms, int hidden, const float* const* weights_host, const float* const* biases_host,
                   float* packed_host);
+
+/* ---- neural spline flow (NSF; ABI 32) ---------------------------------------------------------------------------------------
+ * What the reference's SMC example asks zuko for (examples/smc_example.py:82, flow_class="NSF"; flows/torch/flows.py:155-164).
+ * zuko is absent: the flow is this repository's statement of its documented MonotonicRQSTransform (aspire_amd/flows.py NSFFlow,
+ * csrc/asmc_nsf_dev.h; UNVERIFIED against the package) - x' = (x - loc) / scale, then n_layers masked autoregressive transforms
+ * whose MLP  dims -> hidden -> hidden -> dims (3 bins - 1)  (ReLU, MADE masks folded into the weights) emits per coordinate i the
+ * rows i (3 bins - 1) + [0, bins) = widths, the next `bins` = heights, the last bins - 1 = interior derivatives of a monotonic
+ * rational-quadratic spline on [-5, 5] (the identity outside);  log q(x) = N(z; 0, I) + sum log J - sum log scale.
+ *   asmc_nsf_pack_floats / asmc_nsf_pack (host only): weights_host[3t+0..2] / biases_host[3t+0..2] = the three MASKED dense
+ *     layers of transform t in torch.nn.Linear layout; < 0 = unsupported shape (1 <= dims <= 32, hidden in {32, 64}, bins = 8).
+ * The packed block goes into an asmc_coupling with kind = ASMC_FLOW_NSF, affine = 0 and reserved = bins.  asmc_coupling_logprob
+ * (one pass per transform; profile label k_nsf_logprob) and asmc_coupling_sample (a transform is inverted by at most `dims`
+ * passes, stopping at the first that changes no bit; k_nsf_sample; ASMC_NSF_SAMPLE_ALL_PASSES in the environment runs them all)
+ * take it; asmc_pcn_mutate_flow(_enqueue) runs its un-fused step loop around the density kernel (no one-kernel step for this
+ * kind).  Split-fp16 layers only: a NaN or +-inf coordinate, or an operand beyond the fp16 range, gives a NaN density. */
+int64_t asmc_nsf_pack_floats(int dims, int n_transforms, int hidden, int bins);
+int asmc_nsf_pack(int dims, int n_transforms, int hidden, int bins, const float* const* weights_host,
+                  const float* const* biases_host, float* packed_host);
 
 /* asmc_pcn_mutate_flow: asmc_pcn_mutate with the proposal density q given by a coupling flow instead
  * of a built-in mixture (params->log_q is ignored): per step propose -> log q(x') on the MFMA ->

@@ -37,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "aspire_amd", "csrc")
 # the translation units whose kernels carry vector instructions inside asm statements (split2_f16 / split8_f16 / split4_range
 # of asmc_flow_dev.h, through asmc_flow16_dev.h as well); tests/test_abi_and_layout.py checks that no other one does
-SOURCES = ("asmc_flow16.hip", "asmc_flow.hip", "asmc_pcn_fused.hip")
+SOURCES = ("asmc_flow16.hip", "asmc_flow.hip", "asmc_nsf.hip", "asmc_pcn_fused.hip")
 HIPCC = "/opt/rocm/bin/hipcc"
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-Wno-unused-function"]
 
