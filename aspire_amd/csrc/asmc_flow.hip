@@ -121,8 +121,8 @@ __global__ __launch_bounds__(FLOW_THREADS) void k_coupling_logprob(int64_t n, in
             for (int i = 0; i < H / 2; i++) {
                 const int jp = hh * (H / 2) + i;  // padded dims: loc = 0, scale = 1 are not stored, keep them at zero
                 const bool real = jp < dh;
-                xa[tt][i] = real ? flow_standardise((float)ra[tt][i], loc[jp], scale[jp], 1.0f / scale[jp]) : 0.0f;
-                xb[tt][i] = real ? flow_standardise((float)rb[tt][i], loc[dh + jp], scale[dh + jp], 1.0f / scale[dh + jp]) : 0.0f;
+                xa[tt][i] = real ? flow_standardise_inf((float)ra[tt][i], loc[jp], scale[jp], 1.0f / scale[jp]) : 0.0f;
+                xb[tt][i] = real ? flow_standardise_inf((float)rb[tt][i], loc[dh + jp], scale[dh + jp], 1.0f / scale[dh + jp]) : 0.0f;
             }
         }
         if (PREFETCH && it + 1 < rounds) load_raw(((it + 1) * gridDim.x + blockIdx.x) * FLOW_WAVES + wave);
@@ -411,6 +411,9 @@ bool asmc_flow_math_split() {
 
 static int flow_half_pad(int dims) { return ((dims / 2 + 15) / 16) * 16; }
 
+// what asmc_coupling_pack_floats, asmc_coupling_pack and asmc_coupling_logprob take (layout 0 up to 32 dims, layout 1 above)
+#define ASMC_COUPLING_SHAPES "dims even and <= 128, hidden in {32,64,128}"
+
 static bool flow_supported(int dims, int hidden) {  // (layout 0: 32-particle tiles; dims > 32 take layout 1, asmc_flow16.hip)
     const int H = flow_half_pad(dims);
     return dims <= 32 && dims >= 2 && dims % 2 == 0 && (H == 16 || H == 32) && (hidden == 32 || hidden == 64 || hidden == 128);
@@ -422,7 +425,7 @@ extern "C" int64_t asmc_coupling_pack_floats(int dims, int n_layers, int hidden)
     if (asmc_flow_layout(ASMC_FLOW_COUPLING, dims, hidden) == 1 && n_layers >= 1)  // 32 < dims <= 128: 16-particle groups (asmc_flow16.hip)
         return asmc_flow16_pack_floats(ASMC_FLOW_COUPLING, dims, n_layers, hidden);
     if (!flow_supported(dims, hidden) || n_layers < 1) {
-        asmc_set_error("asmc_coupling_pack_floats: unsupported flow (dims even and <= 64, hidden in {32,64,128})");
+        asmc_set_error("asmc_coupling_pack_floats: unsupported flow (" ASMC_COUPLING_SHAPES ")");
         return ASMC_ERR_UNSUPPORTED;
     }
     return (int64_t)n_layers * flow_layer_floats(flow_half_pad(dims), hidden);
@@ -510,7 +513,7 @@ extern "C" int asmc_coupling_pack(int dims, int n_layers, int hidden, const floa
     if (asmc_flow_layout(ASMC_FLOW_COUPLING, dims, hidden) == 1 && n_layers >= 1)
         return asmc_flow16_pack(ASMC_FLOW_COUPLING, dims, n_layers, hidden, weights_host, biases_host, packed_host);
     if (!flow_supported(dims, hidden) || n_layers < 1) {
-        asmc_set_error("asmc_coupling_pack: unsupported flow (dims even and <= 128, hidden in {32,64,128})");
+        asmc_set_error("asmc_coupling_pack: unsupported flow (" ASMC_COUPLING_SHAPES ")");
         return ASMC_ERR_UNSUPPORTED;
     }
     return flow_pack_layers("asmc_coupling_pack", flow_half_pad(dims), dims / 2, n_layers, hidden, weights_host, biases_host, packed_host);
@@ -692,7 +695,7 @@ extern "C" int asmc_coupling_logprob(asmc_ctx* ctx, int64_t n, int x_dtype, cons
         return ASMC_ERR_ARG;
     }
     if (!flow_supported(flow->dims, flow->hidden) || flow->n_layers < 1) {
-        asmc_set_error("asmc_coupling_logprob: unsupported flow (dims even and <= 64, hidden in {32,64,128})");
+        asmc_set_error("asmc_coupling_logprob: unsupported flow (" ASMC_COUPLING_SHAPES ")");
         return ASMC_ERR_UNSUPPORTED;
     }
     if (x_dtype == ASMC_F64) return dispatch_flow<double>(ctx, n, (const double*)x_dev, flow, out_dev, st);

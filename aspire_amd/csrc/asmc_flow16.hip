@@ -198,7 +198,7 @@ __global__ __launch_bounds__(THREADS) void k_flow16_logprob(int64_t n, int d, co
         for (int s = 0; s < SL; s++) {
             const int j = f16_nat(KIND, D, d, f16_coord(s, h));
             const float xv = (valid && j >= 0) ? (float)x[row * d + j] : 0.0f;
-            xf.set(s, j >= 0 ? flow_standardise(xv, s_loc[s * 4 + h], s_loc[D + s * 4 + h], s_loc[2 * D + s * 4 + h]) : 0.0f);
+            xf.set(s, j >= 0 ? flow_standardise_inf(xv, s_loc[s * 4 + h], s_loc[D + s * 4 + h], s_loc[2 * D + s * 4 + h]) : 0.0f);
         }
         // (the affine form as a compile-time constant of each branch: asmc_flow16_dev.h f16_layer)
         const float val = (!FD::MAF || form == 0) ? f16_logprob<FD, W, THREADS, 0>(xf, n_layers, s_bias, stream, lane, ladj0, base_const, 0)

@@ -16,6 +16,16 @@ __device__ __forceinline__ float flow_standardise(float x, float loc, float scal
     return fmaf(r, rcp, q0);
 }
 
+// ... for the stand-alone density kernels: an infinite quotient stays infinite.  Above, r = a - scale q0 is inf - inf = NaN at a
+// +-inf coordinate, so a row at infinity came back NaN even where the coordinate enters the base density alone (a one-layer
+// coupling flow's transformed half), where log q is -inf - what the fp64 modules answer.  Finite rows: the same bits.
+__device__ __forceinline__ float flow_standardise_inf(float x, float loc, float scale, float rcp) {
+    const float a = x - loc;
+    const float q0 = a * rcp;
+    const float r = fmaf(-scale, q0, a);
+    return __builtin_isinf(q0) ? q0 : fmaf(r, rcp, q0);
+}
+
 // two coordinates at once on the packed fp32 instructions (v_pk_add / mul / fma_f32): the same four IEEE operations per element, so the
 // same bits as flow_standardise, in four instructions per PAIR
 typedef float flow_std2 __attribute__((ext_vector_type(2)));
@@ -132,7 +142,9 @@ __device__ __forceinline__ void acc_relu(floatx16 (&acc)[TPW][NB]) {
 #pragma unroll
         for (int nb = 0; nb < NB; nb++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) acc[tt][nb][r] = fmaxf(acc[tt][nb][r], 0.0f);
+            // (the IEEE-754-2019 maximum, v_maximum3_f32: a NaN sticks.  fmaxf answered 0 to a NaN - inf - inf in a hidden unit of a
+            // row with an infinite coordinate - and the row's density came out without it)
+            for (int r = 0; r < 16; r++) acc[tt][nb][r] = __builtin_elementwise_maximum(acc[tt][nb][r], 0.0f);
 }
 
 // out[NBO] += Wt * in, `in` given as NBI accumulator blocks of the previous layer.  Consecutive MFMAs never hit the

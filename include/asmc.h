@@ -625,12 +625,15 @@ int asmc_pcn_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x_dev,
  * log q(x) = -|z|^2 / 2 - d/2 log(2 pi) - sum s - sum log(scale).  fp32 arithmetic on the fp32-input
  * MFMA, result widened to fp64.  zuko (the reference's flow library) is absent: parity unpinned.
  *   asmc_coupling_pack_floats: length of the packed parameter block, or <0 when the shape is
- *     unsupported (dims even, <= 64; hidden in {32, 64, 128}).
+ *     unsupported (dims even, <= 128; hidden in {32, 64, 128}).
  *   asmc_coupling_pack (host only, no GPU): weights_host[3c+0..2] / biases_host[3c+0..2] are the
  *     three dense layers of coupling layer c in torch.nn.Linear layout ([out, in] row-major;
  *     [hidden, d/2], [hidden, hidden], [d, hidden] with output rows s_raw_0.. then t_0..);
  *     writes them in MFMA operand order into packed_host.
- *   asmc_coupling_logprob: out_dev[i] = log q(x_i). */
+ *   asmc_coupling_logprob: out_dev[i] = log q(x_i).  Non-finite rows come out as IEEE arithmetic gives them in the fp64
+ *     statement of the flow: a NaN coordinate gives NaN; a +-inf coordinate gives NaN once it reaches a conditioner, and -inf
+ *     where it enters the base density alone (the transformed half of a one-layer coupling flow); an operand beyond the fp16
+ *     range of the split-fp16 layers gives NaN. */
 #define ASMC_FLOW_COUPLING 0 /* affine coupling layers with alternating half masks (above) */
 #define ASMC_FLOW_MAF 1      /* masked autoregressive transforms (below) */
 #define ASMC_FLOW_NSF 2      /* masked autoregressive rational-quadratic spline transforms (ABI 32, below) */

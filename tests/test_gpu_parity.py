@@ -936,7 +936,7 @@ def test_coupling_flow_split_path_config3_shape(eng):
     (32, 1, 32, 33, "f64"),
     (4, 2, 32, 257, "f64"),     # padded half (2 -> 16)
     (20, 3, 64, 64, "f32"),
-    (64, 2, 128, 777, "f64"),   # H = 32
+    (64, 2, 128, 777, "f64"),   # layout 1 (d > 32): k_flow16_logprob, 16-row groups
     (48, 3, 64, 1, "f64"),
 ])
 def test_coupling_logprob_vs_oracle(eng, oracle, d, n_layers, hidden, n, xdt):
