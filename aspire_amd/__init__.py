@@ -8,9 +8,10 @@ reference's operator interface (`samples`, `samplers`, `aspire`, `flows`, `targe
 from .aspire import Aspire
 from .flows import CouplingFlow, Flow, GaussianFlow, NSFFlow
 from .history import SMCHistory
+from .moves import DEMove, DESnookerMove, StretchMove
 from .samples import MCMCSamples, PTMCMCSamples, Samples, SMCSamples
 from .targets import DiagGaussianMixture
 
 __all__ = ["Aspire", "Samples", "SMCSamples", "MCMCSamples", "PTMCMCSamples", "SMCHistory", "Flow", "GaussianFlow", "CouplingFlow",
-           "NSFFlow", "DiagGaussianMixture"]
+           "NSFFlow", "DiagGaussianMixture", "StretchMove", "DEMove", "DESnookerMove"]
 __version__ = "0.1.0"

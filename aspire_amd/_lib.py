@@ -26,7 +26,7 @@ COUNT_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
 ASMC_BIS_REC = 40
 ASMC_SELECT_THREADS = 262144
 ASMC_STUDENT_MAX_ROWS = 16384
-ASMC_ABI_VERSION = 32
+ASMC_ABI_VERSION = 33
 ASMC_FLOW_COUPLING, ASMC_FLOW_MAF, ASMC_FLOW_NSF = 0, 1, 2  # asmc_coupling.kind
 ASMC_MAX_COUNT_CELLS = 64  # asmc_pcn_set_count_cells
 ASMC_CDF_REC = 9
@@ -264,6 +264,11 @@ SIGNATURES = {
         [_vp, _i64, _i, _i, _vp, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _i, _vp],
     ),
     "asmc_stretch_counts": (_i, [_vp, _i, _pi64, _vp]),
+    "asmc_ensemble_propose": (_i, [_vp, _i64, _i, _i, _vp, _i, _i, _i, _d, _d, _u64, _u32, _u32, _i, _vp, _vp, _vp]),
+    "asmc_ensemble_accept": (
+        _i,
+        [_vp, _i64, _i, _i, _vp, _i, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _i, _vp],
+    ),
     "asmc_rw_propose": (_i, [_vp, _i64, _i, _i, _vp, _i, _d, _vp, _u64, _u64, _u32, _i, _vp, _vp]),
     "asmc_mh_accept": (_i, [_vp, _i64, _i, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _i, _vp]),
     "asmc_mh_counts": (_i, [_vp, _i, _pi64, _vp]),

@@ -1274,6 +1274,37 @@ class HipEngine:
               "asmc_stretch_counts")
         return out
 
+    # ---- DE and snooker moves of the "emcee_smc" / "emcee" samplers (include/asmc.h asmc_ensemble_*) ----------------------------
+    ENSEMBLE_MOVES = {"de": 1, "snooker": 2}  # ASMC_MOVE_DE, ASMC_MOVE_SNOOKER
+
+    def ensemble_propose(self, x, move: str, nsplits: int, group: int, p0: float, p1: float, seed: int, shard: int, step: int,
+                         t: int):
+        """Group-sweep `group` of step `step` of `move` ("de": p0 = g0, p1 = sigma, nsplits 2; "snooker": p0 = gammas, nsplits
+        4): (y [|group|, d] in x's dtype, logf [|group|]).  `t`: the step's index in the mutation's count array (group 0 zeroes
+        that counter; `stretch_counts` reads it)."""
+        n, d = x.shape
+        m = (n - group + nsplits - 1) // nsplits
+        y = torch.empty((m, d), dtype=x.dtype, device=x.device)
+        logf = self.empty(m)
+        check(self.lib.asmc_ensemble_propose(self._ctx, n, d, self._xdt(x), _dptr(x), self.ENSEMBLE_MOVES[move], int(nsplits),
+                                             int(group), float(p0), float(p1), int(seed), int(shard), int(step), int(t), _dptr(y),
+                                             _dptr(logf), self._stream), "asmc_ensemble_propose")
+        return y, logf
+
+    def ensemble_accept(self, x, nsplits: int, group: int, y, logf, beta: float, ll, lp, lq, ll_new, lp_new, lq_new, seed: int,
+                        shard: int, step: int, t: int, logj=None, logj_new=None):
+        """`stretch_accept` for the proposals of `ensemble_propose`."""
+        self._chk3(ll, lp, lq)
+        n, d = x.shape
+        ll_new, lp_new, lq_new = (v.to(torch.float64).contiguous() for v in (ll_new, lp_new, lq_new))
+        if logj is not None:
+            assert logj.dtype == torch.float64 and logj.is_contiguous()
+            logj_new = logj_new.to(torch.float64).contiguous()
+        check(self.lib.asmc_ensemble_accept(self._ctx, n, d, self._xdt(x), _dptr(x), int(nsplits), int(group), _dptr(y),
+                                            _dptr(logf), float(beta), _dptr(ll), _dptr(lp), _dptr(lq), _dptr(logj), _dptr(ll_new),
+                                            _dptr(lp_new), _dptr(lq_new), _dptr(logj_new), int(seed), int(shard), int(step), int(t),
+                                            self._stream), "asmc_ensemble_accept")
+
     # ---- chain recorder of the "minipcn" / "emcee" samplers (include/asmc.h asmc_chain_*) -----------------------------------------
     def free_memory(self) -> int:
         """Bytes of device memory that an allocation can still get."""

@@ -3,7 +3,8 @@
 `HipEmceeSMC` mirrors reference src/aspire/samplers/smc/emcee.py:14-89.  The move is emcee's default, `StretchMove(a=2.0)` on
 `RedBlueMove(nsplits=2, randomize_split=True)` (Goodman & Weare 2010), run by this repository's HIP kernels
 (csrc/asmc_stretch.hip) instead of the third-party `emcee` package, which is absent: parity with its numpy random stream is
-unpinned.
+unpinned.  `moves` also takes DEMove, DESnookerMove and weighted lists of moves, one move per step
+(`aspire_amd.moves`, csrc/asmc_ensemble.hip).
 """
 from __future__ import annotations
 
@@ -12,6 +13,7 @@ import logging
 import numpy as np
 import torch
 
+from .. import moves as ensemble_moves
 from .base import IdentityTransform, track_calls
 from .smc import DEFAULT_BETA_TOLERANCE, SMCSampler
 
@@ -38,6 +40,17 @@ def stretch_move_settings(moves) -> tuple[float, bool]:
     if not 1.0 < a < np.inf:
         raise ValueError(f"the stretch scale a must be finite and > 1, got {a}")
     return a, bool(getattr(moves, "live_dangerously", False))
+
+
+def ensemble_move_settings(engine, moves):
+    """(a, live_dangerously, move_set) of `moves`.  None or one StretchMove: `stretch_move_settings` and move_set None - the
+    stretch kernels alone, as before the DE and snooker moves existed.  Every other value is parsed by `moves.parse_moves` and
+    needs an engine with the DE / snooker entry points, which is checked before any attribute of `moves` is read."""
+    if ensemble_moves.is_default_path(moves):
+        return stretch_move_settings(moves) + (None,)
+    ensemble_moves.require_engine(engine, moves)
+    move_set = ensemble_moves.parse_moves(moves)
+    return 2.0, move_set.live_dangerously, move_set
 
 
 def autocorr_length_check(tau: np.ndarray, n_t: int, tol: float, quiet: bool) -> None:
@@ -93,7 +106,7 @@ class HipEmceeSMC(SMCSampler):
         if unknown:
             raise TypeError(f"sampler_kwargs {unknown} are not supported by the emcee_smc sampler; supported: "
                             f"{', '.join(SAMPLER_KWARGS[:3])} and moves")
-        self._stretch_a, self._move_live_dangerously = stretch_move_settings(self.emcee_moves)
+        self._stretch_a, self._move_live_dangerously, self._move_set = ensemble_move_settings(self.engine, self.emcee_moves)
         self.rng = rng or self.rng or np.random.default_rng()
         return super().sample(
             n_samples, n_steps=n_steps, adaptive=adaptive, target_efficiency=target_efficiency,
@@ -116,6 +129,9 @@ class HipEmceeSMC(SMCSampler):
             raise RuntimeError(RED_BLUE_MESSAGE)
         if n_local < 2:
             raise ValueError(f"the stretch move needs at least two walkers per rank, this rank holds {n_local}")
+        move_set = self._move_set
+        if move_set is not None and n_local < 4:
+            raise ValueError(f"the DE and snooker moves need at least four walkers per rank, this rank holds {n_local}")
         transformed = not (isinstance(T, IdentityTransform) or getattr(T, "is_identity", False))
         ll, lp, lq = particles.log_likelihood, particles.log_prior, particles.log_q
         if transformed:
@@ -135,21 +151,39 @@ class HipEmceeSMC(SMCSampler):
         k_chain = min(n_local, AUTOCORR_WALKERS) if comm.rank == 0 else 0
         chain = torch.empty((nsteps, k_chain, d), dtype=z.dtype, device=z.device) if k_chain and nsteps else None
         self.last_mutation_path = "stretch move: propose / densities / accept per half-sweep (asmc_stretch_*)"
+        if move_set is not None:
+            self.last_mutation_path = (f"ensemble moves ({move_set.names}), one per step: propose / densities / accept per "
+                                       "group-sweep (asmc_ensemble_*, asmc_stretch_*)")
+            schedule = move_set.schedule(seed, nsteps)  # from the mutation's seed: nothing more is taken from self.rng
+
+            def densities(y):
+                if transformed:
+                    x_prop, logj_new = T.inverse(y)
+                    x_prop, logj_new = e.asarray(x_prop, dtype=x.dtype), e.asarray(logj_new)
+                else:
+                    x_prop, logj_new = y, None
+                lq_new = self._flow_log_prob(x_prop)
+                lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
+                return ll_new, lp_new, lq_new, logj_new
         accepted = 0
         for t0 in range(0, nsteps, MAX_CHUNK):
             chunk = min(MAX_CHUNK, nsteps - t0)
             for t in range(t0, t0 + chunk):
-                for half in (0, 1):
-                    y, logf = e.stretch_propose(z, half, a, seed, shard, t, t - t0)
-                    if transformed:
-                        x_prop, logj_new = T.inverse(y)
-                        x_prop, logj_new = e.asarray(x_prop, dtype=x.dtype), e.asarray(logj_new)
-                    else:
-                        x_prop, logj_new = y, None
-                    lq_new = self._flow_log_prob(x_prop)
-                    lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
-                    e.stretch_accept(z, half, y, logf, beta, ll, lp, lq, ll_new, lp_new, lq_new, seed, shard, t, t - t0,
-                                     logj=logj, logj_new=logj_new)
+                if move_set is not None:
+                    ensemble_moves.run_step(e, move_set.specs[schedule[t]], d, z, beta, ll, lp, lq, logj, densities, seed, shard, t,
+                                            t - t0)
+                else:
+                    for half in (0, 1):
+                        y, logf = e.stretch_propose(z, half, a, seed, shard, t, t - t0)
+                        if transformed:
+                            x_prop, logj_new = T.inverse(y)
+                            x_prop, logj_new = e.asarray(x_prop, dtype=x.dtype), e.asarray(logj_new)
+                        else:
+                            x_prop, logj_new = y, None
+                        lq_new = self._flow_log_prob(x_prop)
+                        lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
+                        e.stretch_accept(z, half, y, logf, beta, ll, lp, lq, ll_new, lp_new, lq_new, seed, shard, t, t - t0,
+                                         logj=logj, logj_new=logj_new)
                 if chain is not None:
                     chain[t].copy_(z[:k_chain])
             accepted += int(e.stretch_counts(chunk).sum())

@@ -21,8 +21,9 @@ from .._xp import is_torch_namespace, to_numpy
 from ..history import SMCHistory
 from ..samples import MCMCSamples, PTMCMCSamples, Samples
 from ..targets import DiagGaussianMixture
+from .. import moves as ensemble_moves
 from .base import IdentityTransform, MCMCSampler, track_calls
-from .emcee_smc import MAX_CHUNK, RED_BLUE_MESSAGE, stretch_move_settings
+from .emcee_smc import MAX_CHUNK, RED_BLUE_MESSAGE, ensemble_move_settings
 from .smc import HipSMC
 
 logger = logging.getLogger(__name__)
@@ -259,7 +260,8 @@ EMCEE_KWARGS = ("progress", "moves", "live_dangerously")
 class HipEmcee(ChainSampler):
     """The `"emcee"` sampler (mcmc.py:203-264): emcee's default move, StretchMove(a) on RedBlueMove(nsplits=2,
     randomize_split=True), by the stretch kernels on log_prob of the preconditioned space.  One step is two
-    half-sweeps; the recorder runs after the second.  `moves` / `live_dangerously`: the rules of `HipEmceeSMC`."""
+    half-sweeps; the recorder runs after the second.  `moves` / `live_dangerously`: the rules of `HipEmceeSMC`, DEMove, DESnookerMove
+    and weighted lists of moves included (one move per step: `aspire_amd.moves`)."""
 
     @track_calls
     def sample(self, n_samples: int | None = None, nwalkers: int | None = None, nsteps: int = 500, rng=None, discard=0,
@@ -270,8 +272,8 @@ class HipEmcee(ChainSampler):
         unknown = sorted(set(kwargs) - set(EMCEE_KWARGS))
         if unknown:
             raise TypeError(f"keyword arguments {unknown} are not supported by the emcee sampler; supported: {', '.join(EMCEE_KWARGS)}")
-        a, move_live = stretch_move_settings(kwargs.get("moves"))
         e = self.engine
+        a, move_live, move_set = ensemble_move_settings(e, kwargs.get("moves"))
         rng = rng or self.rng or np.random.default_rng()
         if not (nwalkers or n_samples):
             raise ValueError("give nwalkers or n_samples: the number of walkers defaults to n_samples")
@@ -282,6 +284,8 @@ class HipEmcee(ChainSampler):
             raise RuntimeError(RED_BLUE_MESSAGE)
         if nwalkers < 2:
             raise ValueError(f"the stretch move needs at least two walkers, got {nwalkers}")
+        if move_set is not None and nwalkers < 4:
+            raise ValueError(f"the DE and snooker moves need at least four walkers, got {nwalkers}")
         self._check_chain_memory(nsteps - discard, nwalkers)
         self.history = SMCHistory()
         _, z, logj, ll, lp, T = self._start(nwalkers)
@@ -289,15 +293,23 @@ class HipEmcee(ChainSampler):
         chain = e.chain_alloc(nsteps - discard, nwalkers, self.dims, z.dtype)  # get_chain(discard): those steps are not kept
         lq, zeros = e.full(nwalkers, 0.0), e.full(nwalkers, 0.0)
         self.last_mutation_path = "stretch move: propose / densities / accept per half-sweep (asmc_stretch_*), recorded from the rows"
+        if move_set is not None:
+            self.last_mutation_path = (f"ensemble moves ({move_set.names}), one per step: propose / densities / accept per "
+                                       "group-sweep (asmc_ensemble_*, asmc_stretch_*), recorded from the rows")
+            schedule = move_set.schedule(seed, nsteps)
         accepted = 0
         for t0 in range(0, nsteps, MAX_CHUNK):
             chunk = min(MAX_CHUNK, nsteps - t0)
             for t in range(t0, t0 + chunk):
-                for half in (0, 1):
-                    y, logf = e.stretch_propose(z, half, a, seed, 0, t, t - t0)
-                    ll_new, lp_new, lq_new, logj_new = self._densities(y, T, zeros)
-                    e.stretch_accept(z, half, y, logf, 1.0, ll, lp, lq, ll_new, lp_new, lq_new, seed, 0, t, t - t0, logj=logj,
-                                     logj_new=logj_new)
+                if move_set is not None:
+                    ensemble_moves.run_step(e, move_set.specs[schedule[t]], self.dims, z, 1.0, ll, lp, lq, logj,
+                                            lambda y: self._densities(y, T, zeros), seed, 0, t, t - t0)
+                else:
+                    for half in (0, 1):
+                        y, logf = e.stretch_propose(z, half, a, seed, 0, t, t - t0)
+                        ll_new, lp_new, lq_new, logj_new = self._densities(y, T, zeros)
+                        e.stretch_accept(z, half, y, logf, 1.0, ll, lp, lq, ll_new, lp_new, lq_new, seed, 0, t, t - t0, logj=logj,
+                                         logj_new=logj_new)
                 if t >= discard:
                     self._record(chain, t - discard, z, ll, lp, T)
             accepted += int(e.stretch_counts(chunk).sum())

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ASMC_ABI_VERSION 32
+#define ASMC_ABI_VERSION 33
 
 #define ASMC_OK 0
 #define ASMC_ERR_ARG (-1)
@@ -849,6 +849,51 @@ int asmc_stretch_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x_de
                         uint64_t seed, uint32_t shard, uint32_t step, int t, asmc_stream stream);
 int asmc_stretch_counts(asmc_ctx* ctx, int n_steps, int64_t* counts_host, asmc_stream stream);
 
+/* ---- differential-evolution and snooker moves of the "emcee_smc" / "emcee" samplers (ABI 33) -------------------------------------
+ * emcee's DEMove(sigma, gamma0) on RedBlueMove(nsplits = 2) and DESnookerMove(gammas) on RedBlueMove(nsplits = 4), both with
+ * randomize_split = True (ter Braak 2006; ter Braak & Vrugt 2008), over the same ensemble and log-target as asmc_stretch_*.  A step
+ * t is S = nsplits group-sweeps g = 0 .. S - 1, each  asmc_ensemble_propose -> (caller: densities at y) -> asmc_ensemble_accept;
+ * asmc_stretch_counts reads the counters.  One move per step; a mutation may mix steps of these moves and of asmc_stretch_*
+ * (the counters are shared, the draws are not).  emcee is absent: DESIGN.md §3.26 records the derivation of the snooker factor and
+ * what emcee's release may do differently.
+ * Split: the bijection sigma of asmc_stretch_* unchanged (same counter, same tag 0xA0000000 | shard), read with S in {2, 4}:
+ *   walker i is in group sigma(i) & (S - 1), slot m of group g is the walker k = sigma^-1(S m + g), group g holds
+ *   S_g = ceil((n - g) / S) = (n - g + S - 1) / S walkers.  n >= 4 (DE needs two distinct partners, the snooker four non-empty
+ *   groups); smaller n: ASMC_ERR_ARG.
+ * Draws of slot m of group g at step `step`: block b = Philox4x32-10(counter {m, step, (b << 2) | g, 0x70000000 | shard}, key
+ *   {seed lo, seed hi}); word 3 = 0x70000000 | shard is used by no other stream under the same key (list: asmc_pt_swap, below).
+ *   W(hi, lo, K) = floor(((hi << 32) | lo) K / 2^64), exact;  U(hi, lo): the 53-bit uniform of asmc_stretch_*.
+ *   every move   b = 0: u' = U(w[2], w[3]) (accept variate)
+ *   DE           b = 0: m1 = W(w[0], w[1], S_o);  b = 1: m2' = W(w[0], w[1], S_o - 1), m2 = m2' + (m2' >= m1), and xi = the FIRST
+ *                variate of the default noise generator's Box-Muller pair on (radius word w[2], angle word w[3]) (DESIGN.md §3.2:
+ *                u = (w[2] + 1/2) 2^-32, t = (w[3] + 1/2) 2^-32 turns, xi = sqrt(-2 ln u) cos(2 pi t), table driven, 1e-16 absolute
+ *                against libm).  S_o = (n + g) / 2 walkers in the other half, j1 = sigma^-1(2 m1 + 1 - g), j2 likewise from m2:
+ *                an ordered pair of distinct walkers, uniform.
+ *   SNOOKER      the other groups o_0 < o_1 < o_2; b = 0: c_0 = sigma^-1(4 W(w[0], w[1], S_{o_0}) + o_0);  b = 1: c_1 from (w[0],
+ *                w[1]) and o_1, c_2 from (w[2], w[3]) and o_2;  b = 2: r = floor(w[0] 6 / 2^32), and (z, z1, z2) = the r-th
+ *                permutation of (c_0, c_1, c_2) in lexicographic order: 012, 021, 102, 120, 201, 210.
+ * asmc_ensemble_propose, move = ASMC_MOVE_DE (nsplits = 2, p0 = g0, p1 = sigma, both finite): gamma = g0 (1 + sigma xi);
+ *   y_dev[m, :] = x_k + gamma (x_j2 - x_j1) (fp64 in this order, rounded to x_dtype), logf_dev[m] = 0.
+ * move = ASMC_MOVE_SNOOKER (nsplits = 4, p0 = gammas, finite): per row, in fp64, delta_c = x_k,c - z_c, ss = sum delta_c^2,
+ *   dp = sum delta_c (z1_c - z2_c), r0 = sqrt(ss), proj = dp / r0, y_dev[m, c] = x_k,c + (gammas proj) (delta_c / r0) rounded to
+ *   x_dtype, logf_dev[m] = (d - 1) (log |r0 + gammas proj| - log r0): the step along the line through z and x_k is the difference
+ *   of the projections of z1 and z2 onto it, the factor the Jacobian r^(d - 1) of the polar coordinates around z.
+ *   The two sums run over the 2^lg lanes that share the row, lg = min(6, ceil(log2 d)): lane l adds its coordinates l, l + 2^lg,
+ *   ... in ascending order starting from the first, then a butterfly v <- v + v[lane ^ o] for o = 2^(lg - 1), ..., 1.
+ *   Degenerate slots write no NaN: r0 = 0 or r0 not finite: y = x_k, logf = -inf;  |r0 + gammas proj| = 0 or not finite:
+ *   logf = -inf (the accept step rejects logf = -inf whatever the densities).
+ * Group 0 zeroes the counter of step index t (0 <= t < 2048); every group's accept adds to it.
+ * asmc_ensemble_accept: asmc_stretch_accept on the slots of group g of the S-way split with the accept variate above. */
+#define ASMC_MOVE_DE 1
+#define ASMC_MOVE_SNOOKER 2
+int asmc_ensemble_propose(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x_dev, int move, int nsplits, int group,
+                          double p0, double p1, uint64_t seed, uint32_t shard, uint32_t step, int t, void* y_dev, double* logf_dev,
+                          asmc_stream stream);
+int asmc_ensemble_accept(asmc_ctx* ctx, int64_t n, int d, int x_dtype, void* x_dev, int nsplits, int group, const void* y_dev,
+                         const double* logf_dev, double beta, double* ll_dev, double* lp_dev, double* lq_dev, double* lj_dev,
+                         const double* ll_new_dev, const double* lp_new_dev, const double* lq_new_dev, const double* lj_new_dev,
+                         uint64_t seed, uint32_t shard, uint32_t step, int t, asmc_stream stream);
+
 /* ---- random-walk Metropolis-Hastings and HMC mutations of the "blackjax_smc" sampler (ABI 26) --------------------------------
  * Replace blackjax.rmh / blackjax.hmc inside BlackJAXSMC.mutate (reference src/aspire/samplers/smc/blackjax.py:145-349): one
  * independent chain per particle on the tempered log-target of smc/base.py:507-519.  blackjax and jax are absent: no parity with
@@ -1032,7 +1077,7 @@ int asmc_chain_clear(asmc_ctx* ctx);
  * hi}, U the 53-bit uniform of the pCN accept stream ((k + 1/2) 2^-53), log u by the noise generator's log.  Word 3 = 0x50000000 |
  * r is used by no other stream of the library under the same key: the pCN noise has q | 0x20000000 and q | 0x40000000
  * (q < 2^28) there, the Gamma variates 0x80000000 | a and 0xC0000000 | a, the accept uniform 0xFFFFFFFF, the stretch move
- * 0x60000000 | shard and 0xA0000000 | shard, NUTS 0x60000000 | k.
+ * 0x60000000 | shard and 0xA0000000 | shard, NUTS 0x60000000 | k, the DE and snooker moves 0x70000000 | shard.
  * Every lane that moves a piece of a row recomputes the decision from the same counters (the lanes of one pair sit in one wave
  * and read both log-likelihoods before any of them writes); an accepted row moves as 16-byte vectors where d * sizeof(T) and
  * x_dev allow, element-wise otherwise.  counts_dev [T - 1] (int64, device) += accepted walkers of pair (r, r + 1): block
