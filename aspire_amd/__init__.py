@@ -10,8 +10,8 @@ from .flows import CouplingFlow, Flow, GaussianFlow, NSFFlow
 from .history import SMCHistory
 from .moves import DEMove, DESnookerMove, StretchMove
 from .samples import MCMCSamples, PTMCMCSamples, Samples, SMCSamples
-from .targets import DiagGaussianMixture
+from .targets import DiagGaussianMixture, GaussianMixture
 
 __all__ = ["Aspire", "Samples", "SMCSamples", "MCMCSamples", "PTMCMCSamples", "SMCHistory", "Flow", "GaussianFlow", "CouplingFlow",
-           "NSFFlow", "DiagGaussianMixture", "StretchMove", "DEMove", "DESnookerMove"]
+           "NSFFlow", "DiagGaussianMixture", "GaussianMixture", "StretchMove", "DEMove", "DESnookerMove"]
 __version__ = "0.1.0"

@@ -50,6 +50,18 @@ class AsmcMixture(ctypes.Structure):
     ]
 
 
+class AsmcFullMix(ctypes.Structure):
+    _fields_ = [
+        ("n_components", c_int32),
+        ("has_bounds", c_int32),
+        ("logw_dev", c_void_p),
+        ("mu_dev", c_void_p),
+        ("whiten_dev", c_void_p),
+        ("lower_dev", c_void_p),
+        ("upper_dev", c_void_p),
+    ]
+
+
 class AsmcNutsState(ctypes.Structure):
     _fields_ = [
         ("n", c_int64),
@@ -213,6 +225,7 @@ SIGNATURES = {
     "asmc_gaussian_draw": (_i, [_vp, _i64, _i, _i, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp]),
     "asmc_mixture_logpdf": (_i, [_vp, _i64, _i, _i, _vp, POINTER(AsmcMixture), _vp, _vp]),
     "asmc_mixture_logpdf_premap": (_i, [_vp, _i64, _i, _i, _vp, _vp, POINTER(AsmcMixture), _vp, _vp]),
+    "asmc_fullmix_logpdf": (_i, [_vp, _i64, _i, _i, _vp, POINTER(AsmcFullMix), _vp, _vp, _vp]),
     "asmc_compact_valid": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi64, _vp]),
     "asmc_colsum": (_i, [_vp, _i64, _i, _i, _vp, _pd, _vp]),
     "asmc_centered_gram": (_i, [_vp, _i64, _i, _i, _vp, _pd, _pd, _vp]),

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (ASMC_CDF_EXACT, ASMC_CDF_FAST, ASMC_F32, ASMC_F64, AsmcChainTarget, AsmcCoupling, AsmcMixture, AsmcPcnParams,
+from ._lib import (ASMC_CDF_EXACT, ASMC_CDF_FAST, ASMC_F32, ASMC_F64, AsmcChainTarget, AsmcCoupling, AsmcFullMix, AsmcMixture, AsmcPcnParams,
                    AsmcTransform, check)
 
 CDF_MODES = {"exact": ASMC_CDF_EXACT, "fast": ASMC_CDF_FAST}
@@ -52,6 +52,33 @@ class DeviceMixture:
 
     def c_struct(self) -> AsmcMixture:
         return AsmcMixture(self.n_components, 0, self.logw.data_ptr(), self.mu.data_ptr(), self.prec.data_ptr())
+
+
+@dataclass
+class DeviceFullMix:
+    """Full-covariance Gaussian mixture log-density, optionally inside a closed box, with its tables resident in HBM.
+
+    log sum_c exp(logw[c] - 0.5 * |whiten[c] (x - mu[c])|^2); whiten[c] lower-triangular; logw includes constants.
+    """
+
+    logw: torch.Tensor  # [C]
+    mu: torch.Tensor  # [C, d]
+    whiten: torch.Tensor  # [C, d, d]
+    lower: torch.Tensor | None = None  # [d]
+    upper: torch.Tensor | None = None  # [d]
+
+    @property
+    def n_components(self) -> int:
+        return int(self.mu.shape[0])
+
+    @property
+    def dims(self) -> int:
+        return int(self.mu.shape[1])
+
+    def c_struct(self) -> AsmcFullMix:
+        bounded = self.lower is not None
+        return AsmcFullMix(self.n_components, int(bounded), self.logw.data_ptr(), self.mu.data_ptr(), self.whiten.data_ptr(),
+                           self.lower.data_ptr() if bounded else None, self.upper.data_ptr() if bounded else None)
 
 
 @dataclass
@@ -724,6 +751,29 @@ class HipEngine:
         check(self.lib.asmc_mixture_logpdf(self._ctx, x.shape[0], x.shape[1], self._xdt(x), _dptr(x), ctypes.byref(cs),
                                            _dptr(out), self._stream), "asmc_mixture_logpdf")
         return out
+
+    def make_fullmix(self, logw, mu, whiten, lower=None, upper=None) -> DeviceFullMix:
+        mu = np.atleast_2d(np.asarray(mu, dtype=np.float64))
+        whiten = np.asarray(whiten, dtype=np.float64)
+        logw = np.atleast_1d(np.asarray(logw, dtype=np.float64))
+        C, d = mu.shape
+        assert whiten.shape == (C, d, d) and logw.shape == (C,) and (lower is None) == (upper is None)
+        lo = hi = None
+        if lower is not None:
+            lo = self.asarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (d,)).copy())
+            hi = self.asarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (d,)).copy())
+        return DeviceFullMix(self.asarray(logw), self.asarray(mu), self.asarray(whiten), lo, hi)
+
+    def fullmix_logpdf(self, x: torch.Tensor, tables: DeviceFullMix, want_grad: bool = False):
+        """Log-density [n] of the fp64 / fp32 rows x, and with want_grad the per-row gradient [n, d] (fp64) from the same launch
+        (include/asmc.h asmc_fullmix_logpdf)."""
+        assert x.is_contiguous() and x.dim() == 2
+        out = self.empty(x.shape[0])
+        grad = self.empty((x.shape[0], x.shape[1])) if want_grad else None
+        cs = tables.c_struct()
+        check(self.lib.asmc_fullmix_logpdf(self._ctx, x.shape[0], x.shape[1], self._xdt(x), _dptr(x), ctypes.byref(cs), _dptr(out),
+                                           _dptr(grad), self._stream), "asmc_fullmix_logpdf")
+        return (out, grad) if want_grad else out
 
     def mixture_logpdf_premap(self, x: torch.Tensor, premap: torch.Tensor, mix: DeviceMixture) -> torch.Tensor:
         """log mixture(t) + sum_j h_j t_j^2 at t = clip(a x + b, lo, hi); premap = rows (a, b, lo, hi, h) of d doubles

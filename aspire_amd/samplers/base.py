@@ -16,7 +16,7 @@ import torch
 from .._xp import is_torch, is_torch_namespace, to_numpy
 from ..comm import Comm, default_comm
 from ..samples import Samples, get_default_engine
-from ..targets import DiagGaussianMixture
+from ..targets import DiagGaussianMixture, GaussianMixture
 
 logger = logging.getLogger(__name__)
 
@@ -136,12 +136,18 @@ class Sampler:
         if isinstance(self._log_prior, DiagGaussianMixture):
             lp = self.engine.mixture_logpdf(x_dev, self._log_prior.device_mixture(self.engine))
             view = None
+        elif isinstance(self._log_prior, GaussianMixture) and hasattr(self.engine, "fullmix_logpdf"):
+            lp = self._log_prior.evaluate(self.engine, x_dev)
+            view = None
         else:
             view = self._user_view(x_dev, log_q=log_q_dev)
             lp = self._to_dev(self.log_prior(view))
         if isinstance(self._log_likelihood, DiagGaussianMixture):
             self.n_likelihood_evaluations += n
             ll = self.engine.mixture_logpdf(x_dev, self._log_likelihood.device_mixture(self.engine))
+        elif isinstance(self._log_likelihood, GaussianMixture) and hasattr(self.engine, "fullmix_logpdf"):
+            self.n_likelihood_evaluations += n
+            ll = self._log_likelihood.evaluate(self.engine, x_dev)
         else:
             if view is None:
                 view = self._user_view(x_dev, log_q=log_q_dev)

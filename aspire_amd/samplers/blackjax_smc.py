@@ -16,7 +16,7 @@ import torch
 
 from .._xp import is_torch_namespace
 from ..flows import GaussianFlow
-from ..targets import DiagGaussianMixture
+from ..targets import DiagGaussianMixture, GaussianMixture
 from .base import IdentityTransform, track_calls
 from .smc import DEFAULT_BETA_TOLERANCE, SMCSampler
 
@@ -189,7 +189,7 @@ class HipBlackJAXSMC(SMCSampler):
         if self._builtin_densities():
             return
         numpy_callables = [name for name, f in (("log_likelihood", self._log_likelihood), ("log_prior", self._log_prior))
-                           if not isinstance(f, DiagGaussianMixture)]
+                           if not isinstance(f, (DiagGaussianMixture, GaussianMixture))]
         if numpy_callables and not is_torch_namespace(self.xp):
             raise TypeError(f"algorithm=\"{algorithm}\" takes gradients by torch.autograd: {' and '.join(numpy_callables)} must be "
                             "torch-differentiable callables (construct the sampler with xp=torch), or use algorithm=\"rwmh\"")
@@ -397,12 +397,17 @@ class HipBlackJAXSMC(SMCSampler):
             view = None
             if isinstance(self._log_prior, DiagGaussianMixture):
                 lp = self._log_prior(zz)
+            elif isinstance(self._log_prior, GaussianMixture):
+                lp = self._log_prior.evaluate(self.engine, zz)  # one launch: value and gradient
             else:
                 view = self._user_view(zz, log_q=lq)
                 lp = self._to_dev(self.log_prior(view))
             if isinstance(self._log_likelihood, DiagGaussianMixture):
                 self.n_likelihood_evaluations += n
                 ll = self._log_likelihood(zz)
+            elif isinstance(self._log_likelihood, GaussianMixture):
+                self.n_likelihood_evaluations += n
+                ll = self._log_likelihood.evaluate(self.engine, zz)
             else:
                 if view is None:
                     view = self._user_view(zz, log_q=lq)

@@ -441,6 +441,32 @@ int asmc_mixture_logpdf(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void
  * density at a clamp end. */
 int asmc_mixture_logpdf_premap(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x_dev, const double* premap_dev,
                                const asmc_mixture* density, double* out_dev, asmc_stream stream);
+/* Built-in log-density: full-covariance Gaussian mixture, optionally inside a closed box
+ *   log sum_c exp(logw[c] - 0.5 * |W_c (x - mu[c])|^2),  logw includes constants;
+ * W_c is lower-triangular with W_c^T W_c = the precision of component c (a zero matrix is a flat component).
+ * All pointers are DEVICE pointers (fp64). */
+typedef struct {
+    int32_t n_components;
+    int32_t has_bounds;
+    const double* logw_dev;   /* [C] */
+    const double* mu_dev;     /* [C, d] */
+    const double* whiten_dev; /* [C, d, d] row-major, lower-triangular (entries above the diagonal are not read) */
+    const double* lower_dev;  /* [d] or NULL */
+    const double* upper_dev;  /* [d] or NULL */
+} asmc_fullmix;
+/* asmc_fullmix_logpdf: evaluate the density over the batch; with grad_dev != NULL the same launch also writes the per-row
+ * gradient [n, d] (fp64).  1 <= d <= 128, 1 <= C <= ASMC_MAX_COMPONENTS, fp64 or fp32 rows, x contiguous [n, d] at any
+ * element-aligned address; anything else: ASMC_ERR_UNSUPPORTED before anything is launched.
+ * Value.  Non-finite rows (every component count, every kernel): a row with a NaN coordinate gives NaN - before the bounds are
+ *   looked at; a row with a +-inf coordinate and no NaN gives -inf, by an explicit test of the row (the arithmetic never sees
+ *   it: inf * 0 against a structural or padded zero of W would give NaN); a finite row outside [lower_j, upper_j] in any
+ *   coordinate gives -inf (the ends are inside); a row whose every term logw_c - q_c / 2 is -inf (a row too far for fp64)
+ *   gives -inf.  q_c is the sum of squares of v = W_c (x - mu_c), never r^T (P r), and the value has the same bits whether or
+ *   not grad_dev is given: an accept decision cannot depend on whether a gradient was asked for.
+ * Gradient.  G_i = - sum_c resp_c W_c^T (W_c (x_i - mu_c)), resp_c = exp(term_c - value_i).  A row whose value is not finite
+ *   gets an all-zero gradient row, never NaN. */
+int asmc_fullmix_logpdf(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x_dev, const asmc_fullmix* density,
+                        double* out_dev, double* grad_dev, asmc_stream stream);
 /* asmc_compact_valid: *n_valid_host == n means the population was already compact and NOTHING was copied - the caller keeps
  * using its inputs (the copy of a 1M x 32 population is 0.6 ms; draw_initial_samples almost always lands here). */
 int asmc_compact_valid(asmc_ctx* ctx, int64_t n, int d, int x_dtype, const void* x_dev,
