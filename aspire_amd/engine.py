@@ -326,6 +326,23 @@ class HipEngine:
         for t in (ll, lp, lq):
             assert t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1
 
+    @classmethod
+    def _accept_args(cls, ll, lp, lq, ll_new, lp_new, lq_new, logj, logj_new):
+        """What `stretch_accept`, `ensemble_accept` and `mh_accept` ask of their arrays: carried densities (and log-Jacobian) fp64
+        and contiguous; returns the proposed ones (ll', lp', lq', logj') converted to that."""
+        cls._chk3(ll, lp, lq)
+        ll_new, lp_new, lq_new = (v.to(torch.float64).contiguous() for v in (ll_new, lp_new, lq_new))
+        if logj is not None:
+            assert logj.dtype == torch.float64 and logj.is_contiguous()
+            logj_new = logj_new.to(torch.float64).contiguous()
+        return ll_new, lp_new, lq_new, logj_new
+
+    def _step_counts(self, fn, name: str, n_steps: int) -> np.ndarray:
+        """The accept counts of step indices 0 .. n_steps - 1 read by `fn` (asmc_stretch_counts, asmc_mh_counts) - synchronises."""
+        out = np.zeros(n_steps, dtype=np.int64)
+        check(fn(self._ctx, int(n_steps), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream), name)
+        return out
+
     # ---- weighting -------------------------------------------------------------------------
     def weights_max(self, ll, lp, lq, beta0: float, betas) -> tuple[np.ndarray, int]:
         self._chk3(ll, lp, lq)
@@ -1306,12 +1323,8 @@ class HipEngine:
                        step: int, t: int, logj=None, logj_new=None):
         """Accepts the proposals of `stretch_propose` in place (rows of x, carried densities; logj / logj_new: carried / proposed
         log-Jacobian of a chain in a preconditioned space, both or neither); the count stays on the device."""
-        self._chk3(ll, lp, lq)
         n, d = x.shape
-        ll_new, lp_new, lq_new = (v.to(torch.float64).contiguous() for v in (ll_new, lp_new, lq_new))
-        if logj is not None:
-            assert logj.dtype == torch.float64 and logj.is_contiguous()
-            logj_new = logj_new.to(torch.float64).contiguous()
+        ll_new, lp_new, lq_new, logj_new = self._accept_args(ll, lp, lq, ll_new, lp_new, lq_new, logj, logj_new)
         check(self.lib.asmc_stretch_accept(self._ctx, n, d, self._xdt(x), _dptr(x), int(half), _dptr(y), _dptr(logf), float(beta),
                                            _dptr(ll), _dptr(lp), _dptr(lq), _dptr(logj), _dptr(ll_new), _dptr(lp_new), _dptr(lq_new),
                                            _dptr(logj_new), int(seed), int(shard), int(step), int(t), self._stream),
@@ -1319,10 +1332,7 @@ class HipEngine:
 
     def stretch_counts(self, n_steps: int) -> np.ndarray:
         """Accept counts of step indices 0 .. n_steps - 1 (this rank's walkers) - synchronises."""
-        out = np.zeros(n_steps, dtype=np.int64)
-        check(self.lib.asmc_stretch_counts(self._ctx, int(n_steps), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream),
-              "asmc_stretch_counts")
-        return out
+        return self._step_counts(self.lib.asmc_stretch_counts, "asmc_stretch_counts", n_steps)
 
     # ---- DE and snooker moves of the "emcee_smc" / "emcee" samplers (include/asmc.h asmc_ensemble_*) ----------------------------
     ENSEMBLE_MOVES = {"de": 1, "snooker": 2}  # ASMC_MOVE_DE, ASMC_MOVE_SNOOKER
@@ -1344,12 +1354,8 @@ class HipEngine:
     def ensemble_accept(self, x, nsplits: int, group: int, y, logf, beta: float, ll, lp, lq, ll_new, lp_new, lq_new, seed: int,
                         shard: int, step: int, t: int, logj=None, logj_new=None):
         """`stretch_accept` for the proposals of `ensemble_propose`."""
-        self._chk3(ll, lp, lq)
         n, d = x.shape
-        ll_new, lp_new, lq_new = (v.to(torch.float64).contiguous() for v in (ll_new, lp_new, lq_new))
-        if logj is not None:
-            assert logj.dtype == torch.float64 and logj.is_contiguous()
-            logj_new = logj_new.to(torch.float64).contiguous()
+        ll_new, lp_new, lq_new, logj_new = self._accept_args(ll, lp, lq, ll_new, lp_new, lq_new, logj, logj_new)
         check(self.lib.asmc_ensemble_accept(self._ctx, n, d, self._xdt(x), _dptr(x), int(nsplits), int(group), _dptr(y),
                                             _dptr(logf), float(beta), _dptr(ll), _dptr(lp), _dptr(lq), _dptr(logj), _dptr(ll_new),
                                             _dptr(lp_new), _dptr(lq_new), _dptr(logj_new), int(seed), int(shard), int(step), int(t),
@@ -1529,22 +1535,15 @@ class HipEngine:
                   logj_new=None):
         """Symmetric Metropolis-Hastings accept of the proposals `y` in place (rows of x, carried densities; logj / logj_new as in
         `stretch_accept`); the count stays on the device."""
-        self._chk3(ll, lp, lq)
         n, d = x.shape
-        ll_new, lp_new, lq_new = (v.to(torch.float64).contiguous() for v in (ll_new, lp_new, lq_new))
-        if logj is not None:
-            assert logj.dtype == torch.float64 and logj.is_contiguous()
-            logj_new = logj_new.to(torch.float64).contiguous()
+        ll_new, lp_new, lq_new, logj_new = self._accept_args(ll, lp, lq, ll_new, lp_new, lq_new, logj, logj_new)
         check(self.lib.asmc_mh_accept(self._ctx, n, d, self._xdt(x), _dptr(x), _dptr(y), float(beta), _dptr(ll), _dptr(lp), _dptr(lq),
                                       _dptr(logj), _dptr(ll_new), _dptr(lp_new), _dptr(lq_new), _dptr(logj_new), int(seed), int(gid0),
                                       int(step), int(t), self._stream), "asmc_mh_accept")
 
     def mh_counts(self, n_steps: int) -> np.ndarray:
         """Accept counts of step indices 0 .. n_steps - 1 (this rank's particles) - synchronises."""
-        out = np.zeros(n_steps, dtype=np.int64)
-        check(self.lib.asmc_mh_counts(self._ctx, int(n_steps), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream),
-              "asmc_mh_counts")
-        return out
+        return self._step_counts(self.lib.asmc_mh_counts, "asmc_mh_counts", n_steps)
 
     def hmc_momentum(self, n: int, d: int, minv, seed: int, gid0: int, step: int, t: int):
         """p [n, d] ~ N(0, M), M^-1 = diag(minv) (None: identity).  Zeroes the counter of step index `t`."""

@@ -67,10 +67,19 @@ class MoveSet:
     specs: tuple
     weights: tuple  # normalised
     live_dangerously: bool
+    default: bool = False  # moves=None or one StretchMove: the stretch kernels alone, two walkers suffice, its own path name
 
     @property
     def names(self) -> str:
         return " + ".join(f"{w:.3g} {s.kind}" for s, w in zip(self.specs, self.weights))
+
+    @property
+    def path(self) -> str:
+        """What a sampler's `last_mutation_path` says about a mutation by these moves."""
+        if self.default:
+            return "stretch move: propose / densities / accept per half-sweep (asmc_stretch_*)"
+        return (f"ensemble moves ({self.names}), one per step: propose / densities / accept per group-sweep (asmc_ensemble_*, "
+                "asmc_stretch_*)")
 
     def schedule(self, seed: int, nsteps: int) -> np.ndarray:
         """The move of every step of a mutation, a function of the mutation's seed alone (one move per step, as emcee's

@@ -6,6 +6,7 @@ The constructor contract is the reference's `aspire.samplers` entry-point contra
 from __future__ import annotations
 
 import logging
+import math
 import pickle
 from pathlib import Path
 from typing import Any, Callable
@@ -36,6 +37,16 @@ def track_calls(func):
         return func(self, *args, **kwargs)
 
     return wrapper
+
+
+MAX_CHUNK = 2048  # steps whose accept counts the device holds (ASMC_MAX_PCN_STEPS): one read-back per chunk
+
+
+def pcn_adapt(rho: float, acc: float, target: float, t: int) -> float:
+    """Step-size adaptation of this repository's pCN spec, identical to the device
+    version in k_pcn_adapt: log rho += (acc - target)/(t+1)^0.75, rho clipped to [1e-4, 0.99]."""
+    r = math.exp(math.log(rho) + (acc - target) / (t + 1) ** 0.75)
+    return min(max(r, 1e-4), 0.99)
 
 
 class IdentityTransform:
@@ -107,6 +118,28 @@ class Sampler:
     def fit_preconditioning_transform(self, x):
         return self.preconditioning_transform.fit(x)
 
+    def _transformed(self) -> bool:
+        T = self.preconditioning_transform
+        return not (isinstance(T, IdentityTransform) or getattr(T, "is_identity", False))
+
+    def _enter_preconditioned(self, x: torch.Tensor):
+        """The one entry of a chain into the preconditioned space: T is refitted to the rows x; returns (z = T(x), log|det
+        dT^-1/dz| at z, T), or (x, None, None) under the identity.  `fit` gets the communicator so that sharded populations fit
+        the global moments; on one rank that is `fit(x)` bit for bit for every class of transforms.py (they only ask
+        `comm.sharded`), so the single-rank chain samplers enter here too."""
+        e, T = self.engine, self.preconditioning_transform
+        if not self._transformed():
+            self.fit_preconditioning_transform(x)
+            return x, None, None
+        if getattr(T, "engine", None) is None and hasattr(T, "engine"):
+            T.engine = e
+        try:
+            z = T.fit(x, comm=self.comm)
+        except TypeError:  # a user-supplied transform with the reference's fit(x) signature
+            z = T.fit(x)
+        z = e.asarray(z, dtype=x.dtype)
+        return z, e.asarray(T.inverse(z)[1]), T
+
     def sample(self, n_samples: int) -> Samples:
         raise NotImplementedError
 
@@ -129,31 +162,64 @@ class Sampler:
     def log_prior(self, samples) -> Any:
         return self._log_prior(samples)
 
-    def _eval_prior_likelihood(self, x_dev: torch.Tensor, log_q_dev: torch.Tensor | None = None):
+    def _builtin_density(self, f, differentiable: bool):
+        """How the target `f` is evaluated without the user view - x -> log-density -, or None for a user callable.  The one
+        place a target class is dispatched: the mixture kernel for `DiagGaussianMixture`, `evaluate` for `GaussianMixture` (an
+        engine without its kernel calls it like any callable); `differentiable`: through their torch `__call__` / `evaluate`."""
+        e = self.engine
+        if isinstance(f, DiagGaussianMixture):
+            return f if differentiable else (lambda x: e.mixture_logpdf(x, f.device_mixture(e)))
+        if isinstance(f, GaussianMixture) and (differentiable or hasattr(e, "fullmix_logpdf")):
+            return lambda x: f.evaluate(e, x)
+        return None
+
+    def _eval_prior_likelihood(self, x_dev: torch.Tensor, log_q_dev: torch.Tensor | None = None, differentiable: bool = False):
         """log_prior then log_likelihood at x (prior first and stored on the samples object passed to
-        the likelihood, as reference smc/base.py:512-513 / docs/recipes.rst rely on)."""
-        n = x_dev.shape[0]
-        if isinstance(self._log_prior, DiagGaussianMixture):
-            lp = self.engine.mixture_logpdf(x_dev, self._log_prior.device_mixture(self.engine))
-            view = None
-        elif isinstance(self._log_prior, GaussianMixture) and hasattr(self.engine, "fullmix_logpdf"):
-            lp = self._log_prior.evaluate(self.engine, x_dev)
-            view = None
+        the likelihood, as reference smc/base.py:512-513 / docs/recipes.rst rely on).  `differentiable`: x is part of an
+        autograd graph (split HMC / NUTS); the values keep their graph and the view's `log_prior` is left as the tensor."""
+        prior = self._builtin_density(self._log_prior, differentiable)
+        likelihood = self._builtin_density(self._log_likelihood, differentiable)
+        view = None
+        if prior is not None:
+            lp = prior(x_dev)
         else:
             view = self._user_view(x_dev, log_q=log_q_dev)
             lp = self._to_dev(self.log_prior(view))
-        if isinstance(self._log_likelihood, DiagGaussianMixture):
-            self.n_likelihood_evaluations += n
-            ll = self.engine.mixture_logpdf(x_dev, self._log_likelihood.device_mixture(self.engine))
-        elif isinstance(self._log_likelihood, GaussianMixture) and hasattr(self.engine, "fullmix_logpdf"):
-            self.n_likelihood_evaluations += n
-            ll = self._log_likelihood.evaluate(self.engine, x_dev)
+        if likelihood is not None:
+            self.n_likelihood_evaluations += x_dev.shape[0]
+            ll = likelihood(x_dev)
         else:
             if view is None:
                 view = self._user_view(x_dev, log_q=log_q_dev)
-            view.log_prior = view.array_to_namespace(lp if is_torch_namespace(view.xp) else to_numpy(lp))
+            view.log_prior = lp if differentiable else view.array_to_namespace(lp if is_torch_namespace(view.xp) else to_numpy(lp))
             ll = self._to_dev(self.log_likelihood(view))
         return lp, ll
+
+    def _proposal_densities(self, z_prop, T, x_dtype, log_q=None, inverted=None):
+        """(x', ll', lp', lq', log|J|' or None) at the proposals z' of a chain in the space of T (None: x itself): back to x
+        through T^-1, log q, then prior and likelihood.  `log_q` is the sampler's rule for lq':
+          None              the proposal flow at x', which the callables' view carries as `log_q` (the SMC samplers);
+          a callable        the same by (z', x', log|J|') -> lq' (`HipSMC`: the flow straight from the preconditioned coordinate);
+          a tensor          its first rows, the flow is not asked ("minipcn", "emcee": zeros, the target has no log q term);
+          "prior"           lq' := lp' ("pt_minipcn": the slot carries the prior's value).
+        `inverted` = (x', log|J|', lq' or None) from a propose kernel that applied T^-1 itself: only what is missing runs."""
+        e = self.engine
+        lq_new = None
+        if inverted is not None:
+            x_prop, logj_new, lq_new = inverted
+            if lq_new is None:
+                lq_new = self._flow_log_prob(x_prop)
+        elif T is None:
+            x_prop, logj_new = z_prop, None
+        else:
+            x_prop, logj_new = T.inverse(z_prop)
+            x_prop, logj_new = e.asarray(x_prop, dtype=x_dtype), e.asarray(logj_new)
+        if lq_new is None and (log_q is None or callable(log_q)):
+            lq_new = self._flow_log_prob(x_prop) if log_q is None else log_q(z_prop, x_prop, logj_new)
+        lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
+        if lq_new is None:
+            lq_new = lp_new if isinstance(log_q, str) else log_q[:x_prop.shape[0]]
+        return x_prop, ll_new, lp_new, lq_new, logj_new
 
     def _flow_log_prob(self, x_dev: torch.Tensor) -> torch.Tensor:
         """prior_flow.log_prob(x) (smc/base.py:510); host (numpy-namespace) flows get a host copy."""
@@ -342,6 +408,67 @@ class MCMCSampler(Sampler):
         # set after construction (as the reference does, mcmc.py:82-87) so no IS weights are formed
         out.log_likelihood, out.log_prior, out.log_q = llv, lpv, lqv
         return out
+
+    # ---- the un-fused pCN step loops ------------------------------------------------------------------------
+    def _pcn_split_steps(self, z, ll, lp, lq, ref, st, densities, *, beta, seed, n_steps, target, n_global, gid0=0, step0=0,
+                         logj=None, noise="f64", session=True, fused=None, on_step=None):
+        """`n_steps` pCN / tpCN steps of the rows z in place, densities between a propose and an accept launch, step size and
+        accept counts resident on the device (one read-back per chunk of 2048 steps).  While the engine grants one (`session`;
+        d = 4, 8, 16, 32) the chain runs as a whitened-state session: the state stays coordinate-major on the device, a step is
+        one mat-vec in the propose kernel and an LDS-free accept kernel.  Otherwise propose / accept on the row-major state.
+        ref = (mu, L, Linv, nu); st["rho"]: the step size, updated; `densities(z', inverted=None)`: `_proposal_densities` with the
+        sampler's rule for log q; `logj`: the carried log-Jacobian, which follows the accepted state inside the accept kernel;
+        `fused` = (transform tables, premapped log q arguments): T^-1 (and log q) inside the session's propose kernel;
+        `on_step(step, sess)`: the chain recorder (sess None: the rows are current).  Returns (accept counts per step - global
+        under a count hook -, whether a session ran)."""
+        e = self.engine
+        mu, L, Linv, nu = ref
+        counts, done, in_session = [], 0, False
+        while done < n_steps:
+            chunk = min(n_steps - done, MAX_CHUNK)
+            sess = None
+            if session and hasattr(e, "pcn_ysplit_begin"):
+                sess = e.pcn_ysplit_begin(z, beta, mu, L, Linv, seed, gid0, st["rho"], target, True, nu, noise)
+                session = sess is not None  # (refused: this width has no whitened-state kernels, the engine is not asked again)
+                in_session = in_session or session
+            if sess is None:
+                e.pcn_split_begin(st["rho"])
+            for t in range(chunk):
+                step = step0 + done + t
+                if sess is None:
+                    z_prop, q0, q1 = e.pcn_propose(z, mu, L, Linv, 0.0, seed, gid0, step, nu=nu)
+                    _, ll_new, lp_new, lq_new, logj_new = densities(z_prop)
+                    e.pcn_accept(z, z_prop, ll, lp, lq, ll_new, lp_new, lq_new, q0, q1, beta, seed, gid0, step, logj_old=logj,
+                                 logj_new=logj_new, want_count=False)
+                    e.pcn_split_adapt(n_global, target, t, True)
+                else:
+                    if fused is not None:
+                        _, ll_new, lp_new, lq_new, logj_new = densities(None, e.pcn_ysplit_propose_tr(sess, step, *fused))
+                    else:
+                        _, ll_new, lp_new, lq_new, logj_new = densities(e.pcn_ysplit_propose(sess, step))
+                    e.pcn_ysplit_accept(sess, step, ll, lp, lq, ll_new, lp_new, lq_new, n_global, t, logj=logj, logj_new=logj_new)
+                if on_step is not None:
+                    on_step(step, sess)
+            n_acc, _, st["rho"] = e.pcn_split_end(chunk) if sess is None else e.pcn_ysplit_end(sess, chunk)
+            counts.append(n_acc)
+            done += chunk
+        return (np.concatenate(counts) if counts else np.zeros(0, dtype=np.int64)), in_session
+
+    def _pcn_round_trip_steps(self, z, ll, lp, lq, ref, st, densities, *, beta, seed, n_steps, target, n_global, gid0=0, step0=0,
+                              logj=None):
+        """The same steps with one host round trip each (engines without the split entry points; sharded runs without a count
+        hook): the accept count comes back, the ranks add theirs, the host adapts the step size.  Returns the global counts."""
+        e = self.engine
+        mu, L, Linv, nu = ref
+        counts = np.zeros(n_steps)
+        for t in range(n_steps):
+            z_prop, q0, q1 = e.pcn_propose(z, mu, L, Linv, st["rho"], seed, gid0, step0 + t, nu=nu)
+            _, ll_new, lp_new, lq_new, logj_new = densities(z_prop)
+            n_acc = e.pcn_accept(z, z_prop, ll, lp, lq, ll_new, lp_new, lq_new, q0, q1, beta, seed, gid0, step0 + t, logj_old=logj,
+                                 logj_new=logj_new)
+            counts[t] = float(self.comm.all_gather_f64(np.array([float(n_acc)])).sum())
+            st["rho"] = pcn_adapt(st["rho"], counts[t] / n_global, target, t)
+        return counts
 
     chain_checkpoint_path = "checkpoint"  # mcmc.py:17-23: where a chain checkpoint lies in its file
     chain_dataset_name = "mcmc_chain"

@@ -17,7 +17,7 @@ import torch
 from .._xp import is_torch_namespace
 from ..flows import GaussianFlow
 from ..targets import DiagGaussianMixture, GaussianMixture
-from .base import IdentityTransform, track_calls
+from .base import track_calls
 from .smc import DEFAULT_BETA_TOLERANCE, SMCSampler
 
 logger = logging.getLogger(__name__)
@@ -155,10 +155,6 @@ class HipBlackJAXSMC(SMCSampler):
             resample_method=resample_method)
 
     # ---- options ------------------------------------------------------------------------------------------------------------
-    def _transformed(self) -> bool:
-        T = self.preconditioning_transform
-        return not (isinstance(T, IdentityTransform) or getattr(T, "is_identity", False))
-
     def _builtin_densities(self) -> bool:
         """Both target densities and the proposal density are diagonal Gaussian mixtures in x itself."""
         return (isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
@@ -239,20 +235,8 @@ class HipBlackJAXSMC(SMCSampler):
     def _mutate_rw(self, x, ll, lp, lq, beta, nsteps, seed, gid0):
         """Random-walk Metropolis-Hastings in the preconditioned space z = T(x): propose / densities / accept per step.  One
         evaluation of the three densities per particle and transition."""
-        e, comm, T = self.engine, self.comm, self.preconditioning_transform
-        transformed = self._transformed()
-        if transformed:
-            if getattr(T, "engine", None) is None and hasattr(T, "engine"):
-                T.engine = e
-            try:
-                z = T.fit(x, comm=comm)
-            except TypeError:  # a user-supplied transform with the reference's fit(x) signature
-                z = T.fit(x)
-            z = e.asarray(z, dtype=x.dtype)
-            logj = e.asarray(T.inverse(z)[1])
-        else:
-            self.fit_preconditioning_transform(x)
-            z, logj = x, None
+        e = self.engine
+        z, logj, T = self._enter_preconditioned(x)
         mode, value = self._sigma
         sigma = value if mode == "scalar" else e.asarray(value)
         self.last_mutation_path = "rwmh split: propose / densities / accept per step (asmc_rw_propose, asmc_mh_accept)"
@@ -261,16 +245,10 @@ class HipBlackJAXSMC(SMCSampler):
             chunk = min(MAX_CHUNK, nsteps - t0)
             for t in range(t0, t0 + chunk):
                 y = e.rw_propose(z, sigma, seed, gid0, t, t - t0)
-                if transformed:
-                    x_prop, logj_new = T.inverse(y)
-                    x_prop, logj_new = e.asarray(x_prop, dtype=x.dtype), e.asarray(logj_new)
-                else:
-                    x_prop, logj_new = y, None
-                lq_new = self._flow_log_prob(x_prop)
-                lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
+                _, ll_new, lp_new, lq_new, logj_new = self._proposal_densities(y, T, x.dtype)
                 e.mh_accept(z, y, beta, ll, lp, lq, ll_new, lp_new, lq_new, seed, gid0, t, t - t0, logj=logj, logj_new=logj_new)
             accepted += int(e.mh_counts(chunk).sum())
-        x_new = e.asarray(T.inverse(z)[0], dtype=x.dtype) if transformed else z
+        x_new = z if T is None else e.asarray(T.inverse(z)[0], dtype=x.dtype)
         return x_new, accepted
 
     def _fused_ok(self, x) -> bool:
@@ -387,32 +365,13 @@ class HipBlackJAXSMC(SMCSampler):
     def _target_and_grad(self, z: torch.Tensor, beta: float):
         """(gradient of the tempered log-target, ll, lp, lq) at the fp64 rows z.  Rows whose log-target is not finite contribute no
         gradient; they are rejections whatever the trajectory does."""
-        n = z.shape[0]
         with torch.enable_grad():
             leaf = z.detach().clone().requires_grad_(True)
             # the callables see a view, never the leaf: `torch.asarray(t)` clears requires_grad of a leaf in place (a callable that
             # does this to the view only detaches its own term: the trajectory stays reversible, the accept step exact)
             zz = leaf.view_as(leaf)
             lq = self._flow_log_prob_torch(zz)
-            view = None
-            if isinstance(self._log_prior, DiagGaussianMixture):
-                lp = self._log_prior(zz)
-            elif isinstance(self._log_prior, GaussianMixture):
-                lp = self._log_prior.evaluate(self.engine, zz)  # one launch: value and gradient
-            else:
-                view = self._user_view(zz, log_q=lq)
-                lp = self._to_dev(self.log_prior(view))
-            if isinstance(self._log_likelihood, DiagGaussianMixture):
-                self.n_likelihood_evaluations += n
-                ll = self._log_likelihood(zz)
-            elif isinstance(self._log_likelihood, GaussianMixture):
-                self.n_likelihood_evaluations += n
-                ll = self._log_likelihood.evaluate(self.engine, zz)
-            else:
-                if view is None:
-                    view = self._user_view(zz, log_q=lq)
-                view.log_prior = lp
-                ll = self._to_dev(self.log_likelihood(view))
+            lp, ll = self._eval_prior_likelihood(zz, lq, differentiable=True)
             lpt = (1.0 - beta) * lq + beta * (ll + lp)
             total = torch.where(torch.isfinite(lpt), lpt, torch.zeros_like(lpt)).sum()
             g = torch.autograd.grad(total, leaf, allow_unused=True)[0] if total.requires_grad else None

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import moves as ensemble_moves
-from .base import IdentityTransform, track_calls
+from .base import MAX_CHUNK, track_calls
 from .smc import DEFAULT_BETA_TOLERANCE, SMCSampler
 
 logger = logging.getLogger(__name__)
@@ -22,7 +22,6 @@ logger = logging.getLogger(__name__)
 # emcee/moves/red_blue.py: the check of RedBlueMove.propose, message included
 RED_BLUE_MESSAGE = "It is unadvisable to use a red-blue move with fewer walkers than twice the number of dimensions."
 AUTOCORR_WALKERS = 256  # mcmc_autocorr is computed over the z-chains of this many walkers of rank 0
-MAX_CHUNK = 2048  # steps whose accept counts the device holds (ASMC_MAX_PCN_STEPS): one read-back per chunk
 SAMPLER_KWARGS = ("nsteps", "progress", "live_dangerously", "n_final_steps", "flow_sample_on_engine")
 
 
@@ -42,15 +41,26 @@ def stretch_move_settings(moves) -> tuple[float, bool]:
     return a, bool(getattr(moves, "live_dangerously", False))
 
 
-def ensemble_move_settings(engine, moves):
-    """(a, live_dangerously, move_set) of `moves`.  None or one StretchMove: `stretch_move_settings` and move_set None - the
+def ensemble_move_settings(engine, moves) -> ensemble_moves.MoveSet:
+    """The move set of `moves`.  None or one StretchMove: `stretch_move_settings` as the one spec of the default set - the
     stretch kernels alone, as before the DE and snooker moves existed.  Every other value is parsed by `moves.parse_moves` and
     needs an engine with the DE / snooker entry points, which is checked before any attribute of `moves` is read."""
     if ensemble_moves.is_default_path(moves):
-        return stretch_move_settings(moves) + (None,)
+        a, live = stretch_move_settings(moves)
+        return ensemble_moves.MoveSet((ensemble_moves.MoveSpec("stretch", 2, a),), (1.0,), live, default=True)
     ensemble_moves.require_engine(engine, moves)
-    move_set = ensemble_moves.parse_moves(moves)
-    return 2.0, move_set.live_dangerously, move_set
+    return ensemble_moves.parse_moves(moves)
+
+
+def check_walkers(move_set, n: int, d: int, live_dangerously: bool, held: str | None = None) -> None:
+    """emcee's check of RedBlueMove.propose, and what the kernels' partner draws need; `held`: how the message counts the n."""
+    held = held or f", got {n}"
+    if n < 2 * d and not (live_dangerously or move_set.live_dangerously):
+        raise RuntimeError(RED_BLUE_MESSAGE)
+    if n < 2:
+        raise ValueError(f"the stretch move needs at least two walkers{held}")
+    if not move_set.default and n < 4:
+        raise ValueError(f"the DE and snooker moves need at least four walkers{held}")
 
 
 def autocorr_length_check(tau: np.ndarray, n_t: int, tol: float, quiet: bool) -> None:
@@ -106,7 +116,7 @@ class HipEmceeSMC(SMCSampler):
         if unknown:
             raise TypeError(f"sampler_kwargs {unknown} are not supported by the emcee_smc sampler; supported: "
                             f"{', '.join(SAMPLER_KWARGS[:3])} and moves")
-        self._stretch_a, self._move_live_dangerously, self._move_set = ensemble_move_settings(self.engine, self.emcee_moves)
+        self._move_set = ensemble_move_settings(self.engine, self.emcee_moves)
         self.rng = rng or self.rng or np.random.default_rng()
         return super().sample(
             n_samples, n_steps=n_steps, adaptive=adaptive, target_efficiency=target_efficiency,
@@ -118,72 +128,30 @@ class HipEmceeSMC(SMCSampler):
 
     def mutate(self, particles, beta, n_steps=None):
         """smc/emcee.py:47-89: every rank's shard is its own ensemble of walkers on log_prob(z, beta) (smc/base.py:507-519) in the
-        preconditioned space z = T(x); the stretch move's two half-sweeps per step run on the device, the host enqueues them and
+        preconditioned space z = T(x); a step's group-sweeps (`moves.run_step`) run on the device, the host enqueues them and
         reads the accept counts once (per 2048 steps)."""
-        e, comm, T = self.engine, self.comm, self.preconditioning_transform
-        kw = self.sampler_kwargs
+        e, comm, kw, move_set = self.engine, self.comm, self.sampler_kwargs, self._move_set
         nsteps = int(n_steps if n_steps is not None else kw["nsteps"])
         x = particles.x if particles.x.is_contiguous() else particles.x.contiguous()
         n_local, d = x.shape
-        if n_local < 2 * d and not (kw.get("live_dangerously", False) or self._move_live_dangerously):
-            raise RuntimeError(RED_BLUE_MESSAGE)
-        if n_local < 2:
-            raise ValueError(f"the stretch move needs at least two walkers per rank, this rank holds {n_local}")
-        move_set = self._move_set
-        if move_set is not None and n_local < 4:
-            raise ValueError(f"the DE and snooker moves need at least four walkers per rank, this rank holds {n_local}")
-        transformed = not (isinstance(T, IdentityTransform) or getattr(T, "is_identity", False))
+        check_walkers(move_set, n_local, d, kw.get("live_dangerously", False), f" per rank, this rank holds {n_local}")
         ll, lp, lq = particles.log_likelihood, particles.log_prior, particles.log_q
-        if transformed:
-            if getattr(T, "engine", None) is None and hasattr(T, "engine"):
-                T.engine = e
-            try:
-                z = T.fit(x, comm=comm)
-            except TypeError:  # a user-supplied transform with the reference's fit(x) signature
-                z = T.fit(x)
-            z = e.asarray(z, dtype=x.dtype)
-            logj = e.asarray(T.inverse(z)[1])
-        else:
-            self.fit_preconditioning_transform(x)
-            z, logj = x, None
+        z, logj, T = self._enter_preconditioned(x)
         seed = int(self.rng.integers(0, 2**63 - 1, dtype=np.int64))
-        a, shard = self._stretch_a, int(comm.rank)
+        shard = int(comm.rank)
         k_chain = min(n_local, AUTOCORR_WALKERS) if comm.rank == 0 else 0
         chain = torch.empty((nsteps, k_chain, d), dtype=z.dtype, device=z.device) if k_chain and nsteps else None
-        self.last_mutation_path = "stretch move: propose / densities / accept per half-sweep (asmc_stretch_*)"
-        if move_set is not None:
-            self.last_mutation_path = (f"ensemble moves ({move_set.names}), one per step: propose / densities / accept per "
-                                       "group-sweep (asmc_ensemble_*, asmc_stretch_*)")
-            schedule = move_set.schedule(seed, nsteps)  # from the mutation's seed: nothing more is taken from self.rng
+        self.last_mutation_path = move_set.path
+        schedule = move_set.schedule(seed, nsteps)  # from the mutation's seed: nothing more is taken from self.rng
 
-            def densities(y):
-                if transformed:
-                    x_prop, logj_new = T.inverse(y)
-                    x_prop, logj_new = e.asarray(x_prop, dtype=x.dtype), e.asarray(logj_new)
-                else:
-                    x_prop, logj_new = y, None
-                lq_new = self._flow_log_prob(x_prop)
-                lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
-                return ll_new, lp_new, lq_new, logj_new
+        def densities(y):
+            return self._proposal_densities(y, T, x.dtype)[1:]
+
         accepted = 0
         for t0 in range(0, nsteps, MAX_CHUNK):
             chunk = min(MAX_CHUNK, nsteps - t0)
             for t in range(t0, t0 + chunk):
-                if move_set is not None:
-                    ensemble_moves.run_step(e, move_set.specs[schedule[t]], d, z, beta, ll, lp, lq, logj, densities, seed, shard, t,
-                                            t - t0)
-                else:
-                    for half in (0, 1):
-                        y, logf = e.stretch_propose(z, half, a, seed, shard, t, t - t0)
-                        if transformed:
-                            x_prop, logj_new = T.inverse(y)
-                            x_prop, logj_new = e.asarray(x_prop, dtype=x.dtype), e.asarray(logj_new)
-                        else:
-                            x_prop, logj_new = y, None
-                        lq_new = self._flow_log_prob(x_prop)
-                        lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
-                        e.stretch_accept(z, half, y, logf, beta, ll, lp, lq, ll_new, lp_new, lq_new, seed, shard, t, t - t0,
-                                         logj=logj, logj_new=logj_new)
+                ensemble_moves.run_step(e, move_set.specs[schedule[t]], d, z, beta, ll, lp, lq, logj, densities, seed, shard, t, t - t0)
                 if chain is not None:
                     chain[t].copy_(z[:k_chain])
             accepted += int(e.stretch_counts(chunk).sum())
@@ -198,7 +166,7 @@ class HipEmceeSMC(SMCSampler):
         if comm.sharded:
             tau = np.asarray(comm.all_gather_f64(np.asarray(tau, dtype=np.float64))[0], dtype=np.float64)
         self.history.mcmc_autocorr.append(tau)
-        x_new = e.asarray(T.inverse(z)[0], dtype=x.dtype) if transformed else z
+        x_new = z if T is None else e.asarray(T.inverse(z)[0], dtype=x.dtype)
         if self._global_counts([e.count_nonfinite(lq)[0]])[0]:
             raise ValueError("Log proposal contains NaN values")
         return self._wrap(x_new, ll, lp, lq, beta, like=particles)

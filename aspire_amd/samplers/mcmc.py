@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import logging
 import math
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -22,11 +23,12 @@ from ..history import SMCHistory
 from ..samples import MCMCSamples, PTMCMCSamples, Samples
 from ..targets import DiagGaussianMixture
 from .. import moves as ensemble_moves
-from .base import IdentityTransform, MCMCSampler, track_calls
-from .emcee_smc import MAX_CHUNK, RED_BLUE_MESSAGE, ensemble_move_settings
+from .base import MAX_CHUNK, MCMCSampler, track_calls
+from .emcee_smc import check_walkers, ensemble_move_settings
 from .smc import HipSMC
 
 logger = logging.getLogger(__name__)
+
 
 class ChainSampler(MCMCSampler):
     """What the two samplers share: one rank only, the memory guard, the preconditioned start, the containers."""
@@ -73,20 +75,15 @@ class ChainSampler(MCMCSampler):
                              f"device memory and {free} bytes are free; use last_step_only=True (where the sampler has it), "
                              "fewer steps or fewer walkers")
 
-    def _start(self, n_walkers: int):
-        """Initial walkers from the flow (mcmc.py:49-110) and their image in the preconditioned space: (x, z, logj, ll, lp, T or
-        None).  z is x itself, and logj None, when the transform is the identity."""
-        e, T = self.engine, self.preconditioning_transform
+    def _start(self, n_walkers: int) -> SimpleNamespace:
+        """The run's state, by name: the initial walkers from the flow (mcmc.py:49-110) as their image z in the preconditioned
+        space (a copy of x itself under the identity, T None), the carried log-Jacobian (or None) and densities."""
+        e = self.engine
         init = self.draw_initial_samples(n_walkers)
         x = init.x if init.x.is_contiguous() else init.x.contiguous()
         ll, lp = e.asarray(init.log_likelihood).clone(), e.asarray(init.log_prior).clone()
-        if isinstance(T, IdentityTransform) or getattr(T, "is_identity", False):
-            self.fit_preconditioning_transform(x)
-            return x, x.clone(), None, ll, lp, None
-        if getattr(T, "engine", None) is None and hasattr(T, "engine"):
-            T.engine = e
-        z = e.asarray(T.fit(x), dtype=x.dtype)
-        return x, z, e.asarray(T.inverse(z)[1]), ll, lp, T
+        z, logj, T = self._enter_preconditioned(x)
+        return SimpleNamespace(z=x.clone() if T is None else z, logj=logj, ll=ll, lp=lp, T=T)
 
     def _record(self, chain, slot, z, ll, lp, T):
         """Slot <- the row-major state: a copy, or T^-1 of it by the transform's own kernels where T has device tables."""
@@ -97,17 +94,6 @@ class ChainSampler(MCMCSampler):
             e.chain_record(chain, slot, x=z, ll=ll, lp=lp, transform=T._tables()[1])
         else:
             e.chain_record(chain, slot, x=e.asarray(T.inverse(z)[0], dtype=z.dtype), ll=ll, lp=lp)
-
-    def _densities(self, z_prop, T, zeros):
-        """(ll', lp', lq' = 0, log|J|' or None) at the proposals; the flow is not asked."""
-        e = self.engine
-        if T is None:
-            x_prop, logj_new = z_prop, None
-        else:
-            x_prop, logj_new = T.inverse(z_prop)
-            x_prop, logj_new = e.asarray(x_prop, dtype=z_prop.dtype), e.asarray(logj_new)
-        lp_new, ll_new = self._eval_prior_likelihood(x_prop)
-        return ll_new, lp_new, zeros[:z_prop.shape[0]], logj_new
 
     def _out(self, samples):
         return samples if is_torch_namespace(self.xp) else samples.to_numpy()
@@ -149,19 +135,18 @@ class HipMiniPCN(ChainSampler):
         self.history = SMCHistory()
         self.sampler_kwargs = {"step_fn": step_fn}
         self._pcn_state = {"rho": min(2.38 / math.sqrt(self.dims), 0.99), "step": 0, "nu": None}
-        _, z, logj, ll, lp, T = self._start(n_walkers)
-        mu, L, Linv, nu = self._fit_reference(z, n_walkers, step_fn)
-        seed = int(rng.integers(0, 2**63 - 1, dtype=np.int64))
-        chain = None if last_step_only else e.chain_alloc(n_steps, n_walkers, self.dims, z.dtype)
-        lq, zeros = e.full(n_walkers, 0.0), e.full(n_walkers, 0.0)
-        run = (z, logj, ll, lp, lq, zeros, T, mu, L, Linv, nu, seed, n_steps, float(target_acceptance_rate), chain)
+        run = self._start(n_walkers)
+        z, ll, lp, T = run.z, run.ll, run.lp, run.T
+        run.ref = self._fit_reference(z, n_walkers, step_fn)
+        run.seed = int(rng.integers(0, 2**63 - 1, dtype=np.int64))
+        run.n_steps, run.target = n_steps, float(target_acceptance_rate)
+        chain = run.chain = None if last_step_only else e.chain_alloc(n_steps, n_walkers, self.dims, z.dtype)
+        run.lq, run.zeros = e.full(n_walkers, 0.0), e.full(n_walkers, 0.0)
         builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
         if T is None and builtin:  # (as HipSMC: the fused kernel at every d; also when nothing is recorded)
             acc = self._steps_fused(run)
-        elif T is None:
-            acc = self._steps_ysplit(run)  # (the session declines other widths than 4, 8, 16, 32: the row-major path then)
         else:
-            acc = self._steps_generic(run)
+            acc = self._steps_split(run, builtin)
         self._check_reference_fit()
         self.history.mcmc_acceptance.append(float(np.mean(acc)) / n_walkers)
         self.history.mcmc_step_size.append(float(self._pcn_state["rho"]))
@@ -186,71 +171,49 @@ class HipMiniPCN(ChainSampler):
         """Built-in mixture densities, any d: the whole step loop inside asmc_pcn_mutate, which records into the chain target
         set on the context.  The kernel wants a log q mixture; at beta = 1 its value has no weight (the likelihood's
         stands in)."""
-        e = self.engine
-        z, logj, ll, lp, lq, zeros, T, mu, L, Linv, nu, seed, n_steps, target, chain = run
+        e, chain = self.engine, run.chain
         self.last_mutation_path = "built-in densities: device-side step loop (asmc_pcn_mutate), recorded by its chain target"
         t_ll, t_lp = self._log_likelihood.device_mixture(e), self._log_prior.device_mixture(e)
         st, acc, done = self._pcn_state, [], 0
         try:
-            while done < n_steps:
-                chunk = min(n_steps - done, MAX_CHUNK)
+            while done < run.n_steps:
+                chunk = min(run.n_steps - done, MAX_CHUNK)
                 if chain is not None:
                     e.chain_set(chain, done, 1)
-                n_acc, _, st["rho"] = e.pcn_mutate(z, ll, lp, lq, 1.0, mu, L, Linv, t_ll, t_lp, t_ll, seed, 0, st["rho"], chunk, done,
-                                                   target, 1, "f64", nu)
+                n_acc, _, st["rho"] = e.pcn_mutate(run.z, run.ll, run.lp, run.lq, 1.0, *run.ref[:3], t_ll, t_lp, t_ll, run.seed, 0,
+                                                   st["rho"], chunk, done, run.target, 1, "f64", run.ref[3])
                 acc.extend(n_acc.tolist())
                 done += chunk
         finally:
             if chain is not None:
                 e.chain_clear()
-        self.n_likelihood_evaluations += n_steps * z.shape[0]
+        self.n_likelihood_evaluations += run.n_steps * run.z.shape[0]
         return acc
 
-    def _steps_ysplit(self, run):
-        """Callables, d in {4, 8, 16, 32}: the whitened-state session; the recorder reads the session's state."""
-        e = self.engine
-        z, logj, ll, lp, lq, zeros, T, mu, L, Linv, nu, seed, n_steps, target, chain = run
-        st, acc, done, n = self._pcn_state, [], 0, z.shape[0]
-        while done < n_steps:
-            chunk = min(n_steps - done, MAX_CHUNK)
-            sess = e.pcn_ysplit_begin(z, 1.0, mu, L, Linv, seed, 0, st["rho"], target, True, nu, "f64")
-            if sess is None:
-                return acc + self._steps_generic(run, done)
+    def _steps_split(self, run, builtin: bool):
+        """Every other case: densities between the propose and accept halves (`_pcn_split_steps`).  Callables under the identity
+        at d in {4, 8, 16, 32} run as the whitened-state session, which the recorder reads; every other width, and every chain in
+        a preconditioned space, on the row-major state."""
+        e, T, chain = self.engine, run.T, run.chain
+
+        def densities(z_prop):
+            return self._proposal_densities(z_prop, T, z_prop.dtype, run.zeros)
+
+        def record(t, sess):
+            if sess is not None:
+                e.chain_record(chain, t, sess=sess, ll=run.ll, lp=run.lp)
+            else:
+                self._record(chain, t, run.z, run.ll, run.lp, T)
+
+        acc, in_session = self._pcn_split_steps(run.z, run.ll, run.lp, run.lq, run.ref, self._pcn_state, densities, beta=1.0,
+                                                seed=run.seed, n_steps=run.n_steps, target=run.target, n_global=run.z.shape[0],
+                                                logj=run.logj, session=T is None, on_step=None if chain is None else record)
+        if in_session:
             self.last_mutation_path = "callables: whitened-state session (asmc_pcn_ysplit_*), recorded from the session's state"
-            for t in range(done, done + chunk):
-                x_prop = e.pcn_ysplit_propose(sess, t)
-                ll_new, lp_new, lq_new, _ = self._densities(x_prop, None, zeros)
-                e.pcn_ysplit_accept(sess, t, ll, lp, lq, ll_new, lp_new, lq_new, n, t - done)
-                if chain is not None:
-                    e.chain_record(chain, t, sess=sess, ll=ll, lp=lp)
-            n_acc, _, st["rho"] = e.pcn_ysplit_end(sess, chunk)
-            acc.extend(n_acc.tolist())
-            done += chunk
-        return acc
-
-    def _steps_generic(self, run, done: int = 0):
-        """Every other case, and every chain in a preconditioned space: propose / densities / accept on the row-major state."""
-        e = self.engine
-        z, logj, ll, lp, lq, zeros, T, mu, L, Linv, nu, seed, n_steps, target, chain = run
-        builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
-        self.last_mutation_path = ("preconditioned chain (z = T(x)): " if T is not None else "") + \
-            ("built-in densities by their own kernel: " if builtin else "callables: ") + \
-            "split propose / accept with the step closed on the stream (asmc_pcn_split_*), recorded from the rows"
-        st, acc, n = self._pcn_state, [], z.shape[0]
-        while done < n_steps:
-            chunk = min(n_steps - done, MAX_CHUNK)
-            e.pcn_split_begin(st["rho"])
-            for t in range(done, done + chunk):
-                z_prop, q0, q1 = e.pcn_propose(z, mu, L, Linv, 0.0, seed, 0, t, nu=nu)
-                ll_new, lp_new, lq_new, logj_new = self._densities(z_prop, T, zeros)
-                e.pcn_accept(z, z_prop, ll, lp, lq, ll_new, lp_new, lq_new, q0, q1, 1.0, seed, 0, t, logj_old=logj, logj_new=logj_new,
-                             want_count=False)
-                e.pcn_split_adapt(n, target, t - done, True)
-                if chain is not None:
-                    self._record(chain, t, z, ll, lp, T)
-            n_acc, _, st["rho"] = e.pcn_split_end(chunk)
-            acc.extend(n_acc.tolist())
-            done += chunk
+        else:
+            self.last_mutation_path = ("preconditioned chain (z = T(x)): " if T is not None else "") + \
+                ("built-in densities by their own kernel: " if builtin else "callables: ") + \
+                "split propose / accept with the step closed on the stream (asmc_pcn_split_*), recorded from the rows"
         return acc
 
 
@@ -273,43 +236,33 @@ class HipEmcee(ChainSampler):
         if unknown:
             raise TypeError(f"keyword arguments {unknown} are not supported by the emcee sampler; supported: {', '.join(EMCEE_KWARGS)}")
         e = self.engine
-        a, move_live, move_set = ensemble_move_settings(e, kwargs.get("moves"))
+        move_set = ensemble_move_settings(e, kwargs.get("moves"))
         rng = rng or self.rng or np.random.default_rng()
         if not (nwalkers or n_samples):
             raise ValueError("give nwalkers or n_samples: the number of walkers defaults to n_samples")
         nwalkers, nsteps, discard = int(nwalkers or n_samples), int(nsteps), int(discard)
         if not 0 <= discard < nsteps:
             raise ValueError(f"discard must be in 0 .. nsteps - 1, got {discard} of {nsteps} steps")
-        if nwalkers < 2 * self.dims and not (kwargs.get("live_dangerously", False) or move_live):
-            raise RuntimeError(RED_BLUE_MESSAGE)
-        if nwalkers < 2:
-            raise ValueError(f"the stretch move needs at least two walkers, got {nwalkers}")
-        if move_set is not None and nwalkers < 4:
-            raise ValueError(f"the DE and snooker moves need at least four walkers, got {nwalkers}")
+        check_walkers(move_set, nwalkers, self.dims, kwargs.get("live_dangerously", False))
         self._check_chain_memory(nsteps - discard, nwalkers)
         self.history = SMCHistory()
-        _, z, logj, ll, lp, T = self._start(nwalkers)
+        run = self._start(nwalkers)
+        z, ll, lp, T = run.z, run.ll, run.lp, run.T
         seed = int(rng.integers(0, 2**63 - 1, dtype=np.int64))
         chain = e.chain_alloc(nsteps - discard, nwalkers, self.dims, z.dtype)  # get_chain(discard): those steps are not kept
         lq, zeros = e.full(nwalkers, 0.0), e.full(nwalkers, 0.0)
-        self.last_mutation_path = "stretch move: propose / densities / accept per half-sweep (asmc_stretch_*), recorded from the rows"
-        if move_set is not None:
-            self.last_mutation_path = (f"ensemble moves ({move_set.names}), one per step: propose / densities / accept per "
-                                       "group-sweep (asmc_ensemble_*, asmc_stretch_*), recorded from the rows")
-            schedule = move_set.schedule(seed, nsteps)
+        self.last_mutation_path = move_set.path + ", recorded from the rows"
+        schedule = move_set.schedule(seed, nsteps)
+
+        def densities(y):
+            return self._proposal_densities(y, T, y.dtype, zeros)[1:]
+
         accepted = 0
         for t0 in range(0, nsteps, MAX_CHUNK):
             chunk = min(MAX_CHUNK, nsteps - t0)
             for t in range(t0, t0 + chunk):
-                if move_set is not None:
-                    ensemble_moves.run_step(e, move_set.specs[schedule[t]], self.dims, z, 1.0, ll, lp, lq, logj,
-                                            lambda y: self._densities(y, T, zeros), seed, 0, t, t - t0)
-                else:
-                    for half in (0, 1):
-                        y, logf = e.stretch_propose(z, half, a, seed, 0, t, t - t0)
-                        ll_new, lp_new, lq_new, logj_new = self._densities(y, T, zeros)
-                        e.stretch_accept(z, half, y, logf, 1.0, ll, lp, lq, ll_new, lp_new, lq_new, seed, 0, t, t - t0, logj=logj,
-                                         logj_new=logj_new)
+                ensemble_moves.run_step(e, move_set.specs[schedule[t]], self.dims, z, 1.0, ll, lp, lq, run.logj, densities, seed, 0,
+                                        t, t - t0)
                 if t >= discard:
                     self._record(chain, t - discard, z, ll, lp, T)
             accepted += int(e.stretch_counts(chunk).sum())
@@ -447,7 +400,8 @@ class HipPTMiniPCN(ChainSampler):
             e.ensure_capacity(n_t * W, self.dims)
         self.history = SMCHistory()
         self.sampler_kwargs = {"step_fn": step_fn}
-        _, z, logj, ll, lp, T = self._start(n_t * W)
+        run = self._start(n_t * W)
+        z, logj, ll, lp, T = run.z, run.logj, run.ll, run.lp, run.T
         builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
         if batched:
             why = ("the densities are callables" if not builtin else "the chain runs in a preconditioned space (a transform)" if T is not None
@@ -479,7 +433,8 @@ class HipPTMiniPCN(ChainSampler):
         counts = torch.zeros(max(n_t - 1, 1), dtype=torch.int64, device=betas_dev.device)
         stepper = self._segment_fused if T is None and builtin else self._segment_generic
         self._noise = noise
-        run = (z, logj, ll, lp, lq, T, rows, ladder, states, refs, seed, float(target_acceptance_rate), chains)
+        run.lq, run.rows, run.ladder, run.states, run.refs, run.chains = lq, rows, ladder, states, refs, chains
+        run.seed, run.target = seed, float(target_acceptance_rate)
         refit_every = None if refit_every is None else int(refit_every)
         accepted, done, n_rounds = np.zeros(n_t), 0, 0
         kept0, rounds0 = None, 0  # (batched) the exchange counts when the kept steps begin
@@ -573,44 +528,40 @@ class HipPTMiniPCN(ChainSampler):
     def _segment_fused(self, run, t0: int, chunk: int):
         """Built-in mixture densities under the identity transform: per rung one asmc_pcn_mutate call on its row range with the
         prior's mixture as the log q mixture, recorded by the chain target pointed at the rung's block.  Each call synchronises."""
-        e = self.engine
-        z, logj, ll, lp, lq, T, rows, ladder, states, refs, seed, target, chains = run
+        e, z, states = self.engine, run.z, run.states
         self.last_mutation_path = ("built-in densities: per rung the device-side step loop (asmc_pcn_mutate) at beta_r, recorded by "
                                    "its chain target; exchange by asmc_pt_swap")
         t_ll, t_lp = self._log_likelihood.device_mixture(e), self._log_prior.device_mixture(e)
-        acc = np.zeros(len(rows))
-        for r, sl in enumerate(rows):
-            mu, L, Linv, nu = refs[r]
-            e.chain_set(chains[r], t0, 1)
-            n_acc, _, states[r]["rho"] = e.pcn_mutate(z[sl], ll[sl], lp[sl], lq[sl], float(ladder[r]), mu, L, Linv, t_ll, t_lp, t_lp, seed,
-                                                      r * z[sl].shape[0], states[r]["rho"], chunk, t0, target, 1, self._noise, nu)
+        acc = np.zeros(len(run.rows))
+        for r, sl in enumerate(run.rows):
+            mu, L, Linv, nu = run.refs[r]
+            e.chain_set(run.chains[r], t0, 1)
+            n_acc, _, states[r]["rho"] = e.pcn_mutate(z[sl], run.ll[sl], run.lp[sl], run.lq[sl], float(run.ladder[r]), mu, L, Linv, t_ll,
+                                                      t_lp, t_lp, run.seed, r * z[sl].shape[0], states[r]["rho"], chunk, t0, run.target, 1,
+                                                      self._noise, nu)
             acc[r] = float(np.sum(n_acc))
         self.n_likelihood_evaluations += chunk * z.shape[0]
         return acc
 
     def _segment_generic(self, run, t0: int, chunk: int):
-        """Callables, and every chain in a preconditioned space: per rung the split propose / densities / accept loop of
-        `HipMiniPCN._steps_generic` at beta_r with lq' := lp', recorded from the rows."""
-        e = self.engine
-        z, logj, ll, lp, lq, T, rows, ladder, states, refs, seed, target, chains = run
+        """Callables, and every chain in a preconditioned space: per rung the row-major split loop (`_pcn_split_steps`) at beta_r
+        with lq' := lp', recorded from the rows."""
+        T = run.T
         builtin = isinstance(self._log_likelihood, DiagGaussianMixture) and isinstance(self._log_prior, DiagGaussianMixture)
         self.last_mutation_path = ("preconditioned chain (z = T(x)): " if T is not None else "") + \
             ("built-in densities by their own kernel: " if builtin else "callables: ") + \
             "per rung split propose / accept at beta_r (asmc_pcn_split_*), recorded from the rows; exchange by asmc_pt_swap"
-        acc = np.zeros(len(rows))
-        for r, sl in enumerate(rows):
-            mu, L, Linv, nu = refs[r]
-            zr, llr, lpr, lqr = z[sl], ll[sl], lp[sl], lq[sl]
-            logjr = None if logj is None else logj[sl]
+
+        def densities(z_prop):
+            return self._proposal_densities(z_prop, T, z_prop.dtype, "prior")
+
+        acc = np.zeros(len(run.rows))
+        for r, sl in enumerate(run.rows):
+            zr, llr, lpr = run.z[sl], run.ll[sl], run.lp[sl]
             n = zr.shape[0]
-            e.pcn_split_begin(states[r]["rho"])
-            for t in range(t0, t0 + chunk):
-                z_prop, q0, q1 = e.pcn_propose(zr, mu, L, Linv, 0.0, seed, r * n, t, nu=nu)
-                ll_new, lp_new, _, logj_new = self._densities(z_prop, T, lqr)
-                e.pcn_accept(zr, z_prop, llr, lpr, lqr, ll_new, lp_new, lp_new, q0, q1, float(ladder[r]), seed, r * n, t,
-                             logj_old=logjr, logj_new=logj_new, want_count=False)
-                e.pcn_split_adapt(n, target, t - t0, True)
-                self._record(chains[r], t, zr, llr, lpr, T)
-            n_acc, _, states[r]["rho"] = e.pcn_split_end(chunk)
+            n_acc, _ = self._pcn_split_steps(zr, llr, lpr, run.lq[sl], run.refs[r], run.states[r], densities, beta=float(run.ladder[r]),
+                                             seed=run.seed, n_steps=chunk, target=run.target, n_global=n, gid0=r * n, step0=t0,
+                                             logj=None if run.logj is None else run.logj[sl], session=False,
+                                             on_step=lambda t, _: self._record(run.chains[r], t, zr, llr, lpr, T))
             acc[r] = float(np.sum(n_acc))
         return acc

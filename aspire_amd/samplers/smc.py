@@ -12,6 +12,7 @@ import copy
 import logging
 import math
 import os
+from types import SimpleNamespace
 from typing import Any, Callable
 
 import numpy as np
@@ -22,7 +23,7 @@ from .._xp import is_torch, to_numpy
 from ..history import SMCHistory
 from ..samples import SMCSamples, Samples
 from ..targets import DiagGaussianMixture
-from .base import IdentityTransform, MCMCSampler, track_calls
+from .base import IdentityTransform, MCMCSampler, pcn_adapt, track_calls
 
 logger = logging.getLogger(__name__)
 
@@ -606,124 +607,6 @@ class HipSMC(SMCSampler):
         self.history.mcmc_nu.append(float(nu) if nu <= NU_GAUSSIAN else float("inf"))
         return (*self._upload_reference(mean, L, Linv), (nu if nu <= NU_GAUSSIAN else 0.0))
 
-    def _mutate_preconditioned(self, particles: SMCSamples, x: torch.Tensor, beta: float, n_steps: int, target: float):
-        """smc/minipcn.py:105-132 with a non-trivial preconditioning transform: the chain runs in z = T(x) (refit at
-        every temperature), the tempered log-target there is log p_t(T^-1(z)) + log|det dT^-1/dz| (smc/base.py:507-519).
-        Per step: propose in z -> x', log|J| (asmc_transform_inverse) -> densities at x' -> accept; the carried
-        log-Jacobian follows the accepted state inside the accept kernel."""
-        e, comm, T = self.engine, self.comm, self.preconditioning_transform
-        if getattr(T, "engine", None) is None and hasattr(T, "engine"):
-            T.engine = e
-        ll, lp, lq = particles.log_likelihood, particles.log_prior, particles.log_q
-        n_local = x.shape[0]
-        n_global = self._n_global(particles)
-        gid0 = self._gid0(particles)
-        try:
-            z = T.fit(x, comm=comm)
-        except TypeError:  # a user-supplied transform with the reference's fit(x) signature
-            z = T.fit(x)
-        z = e.asarray(z, dtype=x.dtype)
-        logj = e.asarray(T.inverse(z)[1])
-        mu, L, Linv, nu = self._fit_reference(z, n_global, self.sampler_kwargs.get("step_fn", "tpcn"))
-        st = self._pcn_state
-        if st["rho"] is None:
-            st["rho"] = min(2.38 / math.sqrt(self.dims), 0.99)
-        seed = int(self.rng.integers(0, 2**63 - 1, dtype=np.int64))
-        step0 = st["step"]
-        acc_rates = []
-
-        # log q(x') straight from z' when the flow's data transform and T share their bounded stage (no erfinv round trip)
-        logq_z = None
-        if self.sampler_kwargs.get("flow_from_preconditioned", True) and hasattr(self.prior_flow, "log_prob_from_preconditioned"):
-            logq_z = self.prior_flow.log_prob_from_preconditioned(T)
-
-        def flow_lq(z_prop, x_prop, logj_new):
-            nonlocal logq_z
-            if logq_z is not None and z_prop.dtype in (torch.float64, torch.float32) and z_prop.is_contiguous():
-                try:
-                    return logq_z(z_prop, logj_new)
-                except Exception as exc:  # a row shape the premapped kernel does not take: the round trip from here on
-                    logger.info("log q from the preconditioned coordinate is not available: %s", exc)
-                    logq_z = None
-            return self._flow_log_prob(x_prop)
-
-        def step(t, rho):
-            z_prop, q0, q1 = e.pcn_propose(z, mu, L, Linv, rho, seed, gid0, step0 + t, nu=nu)
-            x_prop, logj_new = T.inverse(z_prop)
-            x_prop, logj_new = e.asarray(x_prop, dtype=x.dtype), e.asarray(logj_new)
-            lq_new = flow_lq(z_prop, x_prop, logj_new)
-            lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
-            return z_prop, q0, q1, ll_new, lp_new, lq_new, logj_new
-
-        if hasattr(e, "pcn_split_begin"):
-            # step size and accept counts stay on the device: the host enqueues step t + 1 while step t runs
-            if comm.sharded:
-                e.set_count_hook(comm, n_global)
-            try:
-                done = 0
-                while done < n_steps and hasattr(e, "pcn_ysplit_begin"):
-                    # whitened-state session on z (d = 4, 8, 16, 32): one mat-vec per step, LDS-free accept; the carried
-                    # log-Jacobian follows the accepted state inside the accept kernel
-                    chunk = min(n_steps - done, 2048)
-                    sess = e.pcn_ysplit_begin(z, beta, mu, L, Linv, seed, gid0, st["rho"], target, True, nu,
-                                              self.sampler_kwargs.get("noise", "f64"))
-                    if sess is None:
-                        break
-                    # inverse transform (and log q, when it is available from z') inside the propose kernel where the
-                    # transform has one bounded stage and nothing periodic
-                    t_dev = None
-                    if (self.sampler_kwargs.get("fuse_transform", True) and hasattr(e, "pcn_ysplit_propose_tr")
-                            and hasattr(T, "_tables") and not np.any(getattr(T, "_periodic", [1]))):
-                        td = T._tables()[1]
-                        if td.hints & 7 in (5, 3):  # ASMC_TR_NO_PERIODIC | NO_PROBIT (logit) / NO_LOGIT (probit)
-                            t_dev = td
-                    for t in range(done, done + chunk):
-                        if t_dev is not None:
-                            x_prop, logj_new, lq_new = e.pcn_ysplit_propose_tr(sess, step0 + t, t_dev,
-                                                                               getattr(logq_z, "fused_args", None))
-                            if lq_new is None:
-                                lq_new = self._flow_log_prob(x_prop)
-                        else:
-                            z_prop = e.pcn_ysplit_propose(sess, step0 + t)
-                            x_prop, logj_new = T.inverse(z_prop)
-                            x_prop, logj_new = e.asarray(x_prop, dtype=x.dtype), e.asarray(logj_new)
-                            lq_new = flow_lq(z_prop, x_prop, logj_new)
-                        lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
-                        e.pcn_ysplit_accept(sess, step0 + t, ll, lp, lq, ll_new, lp_new, lq_new, n_global, t - done,
-                                            logj=logj, logj_new=logj_new)
-                    n_acc, _, st["rho"] = e.pcn_ysplit_end(sess, chunk)
-                    acc_rates.extend((n_acc / n_global).tolist())
-                    done += chunk
-                while done < n_steps:
-                    chunk = min(n_steps - done, 2048)
-                    e.pcn_split_begin(st["rho"])
-                    for t in range(done, done + chunk):
-                        z_prop, q0, q1, ll_new, lp_new, lq_new, logj_new = step(t, 0.0)
-                        e.pcn_accept(z, z_prop, ll, lp, lq, ll_new, lp_new, lq_new, q0, q1, beta, seed, gid0, step0 + t,
-                                     logj_old=logj, logj_new=logj_new, want_count=False)
-                        e.pcn_split_adapt(n_global, target, t - done, True)
-                    n_acc, _, st["rho"] = e.pcn_split_end(chunk)
-                    acc_rates.extend((n_acc / n_global).tolist())
-                    done += chunk
-            finally:
-                if comm.sharded:
-                    e.set_count_hook(None, None)
-        else:
-            for t in range(n_steps):
-                z_prop, q0, q1, ll_new, lp_new, lq_new, logj_new = step(t, st["rho"])
-                n_acc = e.pcn_accept(z, z_prop, ll, lp, lq, ll_new, lp_new, lq_new, q0, q1, beta, seed, gid0, step0 + t,
-                                     logj_old=logj, logj_new=logj_new)
-                tot = float(comm.all_gather_f64(np.array([float(n_acc)])).sum())
-                acc_rates.append(tot / n_global)
-                st["rho"] = pcn_adapt(st["rho"], acc_rates[-1], target, t)
-        st["step"] = step0 + n_steps
-        self.history.mcmc_acceptance.append(float(np.mean(acc_rates)))
-        self.history.mcmc_step_size.append(float(st["rho"]))
-        x_new = e.asarray(T.inverse(z)[0], dtype=x.dtype)
-        if self._global_counts([e.count_nonfinite(lq)[0]])[0]:
-            raise ValueError("Log proposal contains NaN values")
-        return self._wrap(x_new, ll, lp, lq, beta, like=particles)
-
     def _adapt_mode(self) -> int:
         """`asmc_pcn_params.adapt` of the device-side step loops: 1 = the step size adapts after every step (default, the
         specification every test pins); `sampler_kwargs["adapt_lag"] = k` (2 .. 64) holds it for blocks of k steps and applies the
@@ -812,46 +695,38 @@ class HipSMC(SMCSampler):
                 and isinstance(self.preconditioning_transform, IdentityTransform))
 
     def mutate(self, particles: SMCSamples, beta: float, n_steps: int | None = None) -> SMCSamples:
-        """smc/minipcn.py:69-135."""
+        """smc/minipcn.py:69-135.  Under a non-trivial preconditioning transform (smc/minipcn.py:105-132) the chain runs in
+        z = T(x), refitted at every temperature; the tempered log-target there is log p_t(T^-1(z)) + log|det dT^-1/dz|
+        (smc/base.py:507-519) and the carried log-Jacobian follows the accepted state inside the accept kernel."""
         e, comm = self.engine, self.comm
         kwargs = self.sampler_kwargs.copy()
-        n_steps = n_steps or kwargs.pop("n_steps")
-        target = float(kwargs.get("target_acceptance_rate", 0.234))
-        noise = kwargs.get("noise", "f64")
+        m = SimpleNamespace(particles=particles, beta=beta, n_steps=n_steps or kwargs.pop("n_steps"),
+                            target=float(kwargs.get("target_acceptance_rate", 0.234)), noise=kwargs.get("noise", "f64"),
+                            ll=particles.log_likelihood, lp=particles.log_prior, lq=particles.log_q, st=self._pcn_state)
         x = particles.x if particles.x.is_contiguous() else particles.x.contiguous()
-        T = self.preconditioning_transform
-        transformed = not (isinstance(T, IdentityTransform) or getattr(T, "is_identity", False))
-        if transformed:
-            self.last_mutation_path = "preconditioned chain (z = T(x)): split propose / accept around the transform"
-            out = self._mutate_preconditioned(particles, x, beta, n_steps, target)
-            self._check_reference_fit()
-            return out
-        self.fit_preconditioning_transform(particles.x)
-        ll, lp, lq = particles.log_likelihood, particles.log_prior, particles.log_q
-        n_local = x.shape[0]
-        n_global = self._n_global(particles)
-        gid0 = self._gid0(particles)
-        mu, L, Linv, nu = self._fit_reference(x, n_global, kwargs.get("step_fn", "tpcn"), particles.__dict__.get("_moments"))
-        st = self._pcn_state
-        if st["rho"] is None:
-            st["rho"] = min(2.38 / math.sqrt(self.dims), 0.99)
-        seed = int(self.rng.integers(0, 2**63 - 1, dtype=np.int64))
-        step0 = st["step"]
-        acc_rates = []
-        dev_flow = self._device_flow()
+        m.x_dtype, m.n_local = x.dtype, x.shape[0]
+        m.z, m.logj, m.T = self._enter_preconditioned(x)  # (the chain's state: x itself under the identity)
+        m.n_global, m.gid0 = self._n_global(particles), self._gid0(particles)
+        m.ref = self._fit_reference(m.z, m.n_global, kwargs.get("step_fn", "tpcn"),
+                                    None if m.T is not None else particles.__dict__.get("_moments"))
+        if m.st["rho"] is None:
+            m.st["rho"] = min(2.38 / math.sqrt(self.dims), 0.99)
+        m.seed = int(self.rng.integers(0, 2**63 - 1, dtype=np.int64))
+        m.step0 = m.st["step"]
+        m.dev_flow = None if m.T is not None else self._device_flow()
         # whole step loop on the device: always for one rank; sharded when the engine can exchange the accept counts
         # between a step and its adaptation on the stream (asmc_pcn_set_count_hook), else one host round trip per step
-        on_device = not comm.sharded or hasattr(e, "set_count_hook")
-        if comm.sharded and on_device:
-            e.set_count_hook(comm, n_global)
+        m.on_device = not comm.sharded or hasattr(e, "set_count_hook")
+        if comm.sharded and m.on_device:
+            e.set_count_hook(comm, m.n_global)
         try:
-            out = self._mutate_steps(particles, x, ll, lp, lq, beta, n_steps, target, noise, mu, L, Linv, st, seed, step0,
-                                     acc_rates, dev_flow, on_device, n_local, n_global, gid0, nu)
+            out = self._mutate_steps(m)
         finally:
-            if comm.sharded and on_device:
+            if comm.sharded and m.on_device:
                 e.set_count_hook(None, None)
         self._check_reference_fit()
         return out
+
 
     def _check_reference_fit(self):
         """The device-side factorisation of the reference covariance (`engine.reference_factor`) reports behind the mutation
@@ -869,46 +744,39 @@ class HipSMC(SMCSampler):
         if status > 0:
             logger.info("reference covariance factored with jitter (try %d)", status)
 
-    def _mutate_steps(self, particles, x, ll, lp, lq, beta, n_steps, target, noise, mu, L, Linv, st, seed, step0, acc_rates,
-                      dev_flow, on_device, n_local, n_global, gid0, nu=0.0):
+    def _mutate_steps(self, m):
         """The mutation's step loop.  Four code paths, chosen from what the densities are (`last_mutation_path` names the one
-        taken): the flow-proposal loop on the device, the built-in-density loop on the device, arbitrary callables between
-        device-side propose / accept halves, and the same with one host round trip per step."""
-        e = self.engine
-        m = (particles, x, ll, lp, lq, beta, n_steps, target, noise, mu, L, Linv, st, seed, step0, acc_rates, dev_flow, on_device,
-             n_local, n_global, gid0, nu)
-        if self._flow_fused_ok(dev_flow):
-            self._steps_flow_on_device(m)
-        elif self._fused_ok():
-            self._steps_builtin_on_device(m)
-        elif hasattr(e, "pcn_split_begin") and on_device:
-            self._steps_callables_split(m)
+        taken): the flow-proposal loop on the device, the built-in-density loop on the device, arbitrary callables (and every
+        chain in a preconditioned space) between device-side propose / accept halves, and the same with one host round trip per
+        step.  `m`: the mutation's state, by name."""
+        if m.T is None and self._flow_fused_ok(m.dev_flow):
+            acc_rates = self._steps_flow_on_device(m)
+        elif m.T is None and self._fused_ok():
+            acc_rates = self._steps_builtin_on_device(m)
         else:
-            self._steps_callables_round_trip(m)
-        return self._finish_mutation(m)
+            acc_rates = self._steps_callables(m)
+        return self._finish_mutation(m, acc_rates)
 
     def _steps_flow_on_device(self, m):
         """Coupling-flow proposal density evaluated on the matrix cores inside the device-side step loop (BASELINE config 3)."""
-        e, comm = self.engine, self.comm
-        (particles, x, ll, lp, lq, beta, n_steps, target, noise, mu, L, Linv, st, seed, step0, acc_rates, dev_flow, on_device,
-         n_local, n_global, gid0, nu) = m
-        # flow proposal density evaluated on the MFMA inside the device-side step loop (BASELINE config 3)
+        e, comm, st, acc_rates = self.engine, self.comm, m.st, []
+        x, ll, lp, lq, (mu, L, Linv, nu) = m.z, m.ll, m.lp, m.lq, m.ref
         self.last_mutation_path = "flow: device-side step loop (asmc_pcn_mutate_flow; one fused kernel per step where its shape is covered)"
         t_ll = self._log_likelihood.device_mixture(e)
         t_lp = self._log_prior.device_mixture(e)
-        if on_device:
+        if m.on_device:
             done = 0
-            while done < n_steps:
-                chunk = min(n_steps - done, 2048)
-                ahead = chunk == n_steps and n_steps <= 1024 and self._importance_step_follows(beta)
+            while done < m.n_steps:
+                chunk = min(m.n_steps - done, 2048)
+                ahead = chunk == m.n_steps and m.n_steps <= 1024 and self._importance_step_follows(m.beta)
                 if ahead:
                     # the next temperature's importance step (search, resampling, gather, moments) goes onto the stream
                     # right behind the mutation, BEFORE the host waits for either: the GPU does not idle while Python
                     # does the bookkeeping of the finished mutation
-                    handle = e.pcn_mutate_flow_enqueue(x, ll, lp, lq, beta, mu, L, Linv, t_ll, t_lp, dev_flow, seed, gid0,
-                                                       st["rho"], chunk, step0, target, self._adapt_mode(), noise, nu)
-                    out = self._wrap(x, ll, lp, lq, beta, like=particles)
-                    ok = out.speculate_importance_step(self.current_target_efficiency(beta), self._beta_tolerance, self.rng,
+                    handle = e.pcn_mutate_flow_enqueue(x, ll, lp, lq, m.beta, mu, L, Linv, t_ll, t_lp, m.dev_flow, m.seed, m.gid0,
+                                                       st["rho"], chunk, m.step0, m.target, self._adapt_mode(), m.noise, nu)
+                    out = self._wrap(x, ll, lp, lq, m.beta, like=m.particles)
+                    ok = out.speculate_importance_step(self.current_target_efficiency(m.beta), self._beta_tolerance, self.rng,
                                                        resample_mode=self.resample_mode, resample_method=self.resample_method,
                                                        moments_n=self._speculated_moments_n(out), defer=True,
                                                        shard_layout=self.shard_layout, factor_ahead=self._factor_ahead())
@@ -916,131 +784,134 @@ class HipSMC(SMCSampler):
                     if ok:
                         st["prewrapped"] = out  # the step's results are collected when the next iteration asks for them
                 else:
-                    n_acc, rho_hist, rho = e.pcn_mutate_flow(x, ll, lp, lq, beta, mu, L, Linv, t_ll, t_lp, dev_flow, seed,
-                                                             gid0, st["rho"], chunk, step0 + done, target, self._adapt_mode(), noise, nu)
+                    n_acc, rho_hist, rho = e.pcn_mutate_flow(x, ll, lp, lq, m.beta, mu, L, Linv, t_ll, t_lp, m.dev_flow, m.seed,
+                                                             m.gid0, st["rho"], chunk, m.step0 + done, m.target, self._adapt_mode(),
+                                                             m.noise, nu)
                 st["rho"] = rho
                 st["lq_checked"] = hasattr(e, "pcn_lq_nan")
-                acc_rates.extend((n_acc / n_global).tolist())
+                acc_rates.extend((n_acc / m.n_global).tolist())
                 done += chunk
                 n_bad = e.pcn_flow_nonfinite() if hasattr(e, "pcn_flow_nonfinite") else 0
                 if n_bad > 0:
                     # beta = 1: the steps do not look at the flow density (the tempered target has no log q term), so such a
                     # proposal was accepted or rejected on the targets alone and the refresh behind the steps found the NaN
                     what = ("particles moved at beta = 1 carry a non-finite flow density (the accept test has no log q term there; "
-                            "the check of the carried log q raises on them)" if beta == 1.0
+                            "the check of the carried log q raises on them)" if m.beta == 1.0
                             else "proposals had a non-finite flow density and were rejected")
                     logger.warning(f"{n_bad} {what} (a badly scaled flow overflows the fp16 operand pairs of the flow kernel; "
                                    "ASMC_FLOW_MATH=f32 uses fp32 MFMAs)")
         else:
-            for t in range(n_steps):
-                n_acc, _, _ = e.pcn_mutate_flow(x, ll, lp, lq, beta, mu, L, Linv, t_ll, t_lp, dev_flow, seed, gid0,
-                                                st["rho"], 1, step0 + t, target, False, noise, nu)
+            for t in range(m.n_steps):
+                n_acc, _, _ = e.pcn_mutate_flow(x, ll, lp, lq, m.beta, mu, L, Linv, t_ll, t_lp, m.dev_flow, m.seed, m.gid0,
+                                                st["rho"], 1, m.step0 + t, m.target, False, m.noise, nu)
                 tot = float(comm.all_gather_f64(np.array([float(n_acc[0])])).sum())
-                acc_rates.append(tot / n_global)
-                st["rho"] = pcn_adapt(st["rho"], acc_rates[-1], target, t)
-        self.n_likelihood_evaluations += n_steps * n_local
+                acc_rates.append(tot / m.n_global)
+                st["rho"] = pcn_adapt(st["rho"], acc_rates[-1], m.target, t)
+        self.n_likelihood_evaluations += m.n_steps * m.n_local
+        return acc_rates
 
     def _steps_builtin_on_device(self, m):
         """Built-in densities (DiagGaussianMixture targets, analytic proposal): the whole loop in asmc_pcn_mutate."""
-        e, comm = self.engine, self.comm
-        (particles, x, ll, lp, lq, beta, n_steps, target, noise, mu, L, Linv, st, seed, step0, acc_rates, dev_flow, on_device,
-         n_local, n_global, gid0, nu) = m
+        e, comm, st, acc_rates = self.engine, self.comm, m.st, []
+        x, ll, lp, lq, (mu, L, Linv, nu) = m.z, m.ll, m.lp, m.lq, m.ref
         self.last_mutation_path = "built-in densities: device-side step loop (asmc_pcn_mutate)"
         t_ll = self._log_likelihood.device_mixture(e)
         t_lp = self._log_prior.device_mixture(e)
         t_lq = self.prior_flow.device_mixture(e)
-        if on_device:
+        if m.on_device:
             done = 0
-            while done < n_steps:
-                chunk = min(n_steps - done, 2048)
-                n_acc, rho_hist, rho = e.pcn_mutate(x, ll, lp, lq, beta, mu, L, Linv, t_ll, t_lp, t_lq, seed,
-                                                    gid0, st["rho"], chunk, step0 + done, target, self._adapt_mode(), noise, nu)
+            while done < m.n_steps:
+                chunk = min(m.n_steps - done, 2048)
+                n_acc, rho_hist, rho = e.pcn_mutate(x, ll, lp, lq, m.beta, mu, L, Linv, t_ll, t_lp, t_lq, m.seed, m.gid0, st["rho"],
+                                                    chunk, m.step0 + done, m.target, self._adapt_mode(), m.noise, nu)
                 st["rho"] = rho
                 st["lq_checked"] = hasattr(e, "pcn_lq_nan")
-                acc_rates.extend((n_acc / n_global).tolist())
+                acc_rates.extend((n_acc / m.n_global).tolist())
                 done += chunk
         else:
-            for t in range(n_steps):
-                n_acc, _, _ = e.pcn_mutate(x, ll, lp, lq, beta, mu, L, Linv, t_ll, t_lp, t_lq, seed, gid0,
-                                           st["rho"], 1, step0 + t, target, False, noise, nu)
+            for t in range(m.n_steps):
+                n_acc, _, _ = e.pcn_mutate(x, ll, lp, lq, m.beta, mu, L, Linv, t_ll, t_lp, t_lq, m.seed, m.gid0,
+                                           st["rho"], 1, m.step0 + t, m.target, False, m.noise, nu)
                 tot = float(comm.all_gather_f64(np.array([float(n_acc[0])])).sum())
-                acc_rates.append(tot / n_global)
-                st["rho"] = pcn_adapt(st["rho"], acc_rates[-1], target, t)
-        self.n_likelihood_evaluations += n_steps * n_local
+                acc_rates.append(tot / m.n_global)
+                st["rho"] = pcn_adapt(st["rho"], acc_rates[-1], m.target, t)
+        self.n_likelihood_evaluations += m.n_steps * m.n_local
+        return acc_rates
 
-    def _steps_callables_split(self, m):
-        """Arbitrary callables between the propose and accept halves; step size and accept counts stay on the device."""
-        e, comm = self.engine, self.comm
-        (particles, x, ll, lp, lq, beta, n_steps, target, noise, mu, L, Linv, st, seed, step0, acc_rates, dev_flow, on_device,
-         n_local, n_global, gid0, nu) = m
-        # arbitrary callables between propose and accept; step size and accept counts stay on the device (the exchange
-        # hook of sharded runs is already installed by the caller), so the host enqueues step t + 1 while step t runs
-        done = 0
-        self.last_mutation_path = "callables: split propose / accept with the step closed on the stream (asmc_pcn_split_*)"
-        while done < n_steps and hasattr(e, "pcn_ysplit_begin"):
-            # whitened-state session (d = 4, 8, 16, 32): the chain state stays coordinate-major on the device, a step is
-            # one mat-vec in the propose kernel and an LDS-free accept kernel
-            chunk = min(n_steps - done, 2048)
-            sess = e.pcn_ysplit_begin(x, beta, mu, L, Linv, seed, gid0, st["rho"], target, True, nu, noise)
-            if sess is None:
-                break
-            self.last_mutation_path = "callables: whitened-state session (asmc_pcn_ysplit_*)"
-            for t in range(done, done + chunk):
-                x_prop = e.pcn_ysplit_propose(sess, step0 + t)
-                lq_new = self._flow_log_prob(x_prop)
-                lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
-                e.pcn_ysplit_accept(sess, step0 + t, ll, lp, lq, ll_new, lp_new, lq_new, n_global, t - done)
-            n_acc, _, st["rho"] = e.pcn_ysplit_end(sess, chunk)
-            acc_rates.extend((n_acc / n_global).tolist())
-            done += chunk
-        while done < n_steps:
-            chunk = min(n_steps - done, 2048)
-            e.pcn_split_begin(st["rho"])
-            for t in range(done, done + chunk):
-                x_prop, q0, q1 = e.pcn_propose(x, mu, L, Linv, 0.0, seed, gid0, step0 + t, nu=nu)
-                lq_new = self._flow_log_prob(x_prop)
-                lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
-                e.pcn_accept(x, x_prop, ll, lp, lq, ll_new, lp_new, lq_new, q0, q1, beta, seed, gid0, step0 + t,
-                             want_count=False)
-                e.pcn_split_adapt(n_global, target, t - done, True)
-            n_acc, _, st["rho"] = e.pcn_split_end(chunk)
-            acc_rates.extend((n_acc / n_global).tolist())
-            done += chunk
 
-    def _steps_callables_round_trip(self, m):
-        """Arbitrary callables, one host round trip per step (engines without the split entry points; sharded without a count hook)."""
-        e, comm = self.engine, self.comm
-        (particles, x, ll, lp, lq, beta, n_steps, target, noise, mu, L, Linv, st, seed, step0, acc_rates, dev_flow, on_device,
-         n_local, n_global, gid0, nu) = m
-        self.last_mutation_path = "callables: split propose / accept, one host round trip per step"
-        for t in range(n_steps):
-            x_prop, q0, q1 = e.pcn_propose(x, mu, L, Linv, st["rho"], seed, gid0, step0 + t, nu=nu)
-            lq_new = self._flow_log_prob(x_prop)
-            lp_new, ll_new = self._eval_prior_likelihood(x_prop, lq_new)
-            n_acc = e.pcn_accept(x, x_prop, ll, lp, lq, ll_new, lp_new, lq_new, q0, q1, beta, seed, gid0,
-                                 step0 + t)
-            tot = float(comm.all_gather_f64(np.array([float(n_acc)])).sum())
-            acc_rates.append(tot / n_global)
-            st["rho"] = pcn_adapt(st["rho"], acc_rates[-1], target, t)
+    def _flow_log_q_from(self, T):
+        """log q(x') straight from z' where the flow's data transform and T share their bounded stage (no erfinv round trip):
+        (the rule for `_proposal_densities`, the arguments for the fused-transform propose kernel), or (None, None)."""
+        logq_z = None
+        if self.sampler_kwargs.get("flow_from_preconditioned", True) and hasattr(self.prior_flow, "log_prob_from_preconditioned"):
+            logq_z = self.prior_flow.log_prob_from_preconditioned(T)
+        if logq_z is None:
+            return None, None
 
-    def _finish_mutation(self, m):
+        def flow_lq(z_prop, x_prop, logj_new):
+            nonlocal logq_z
+            if logq_z is not None and z_prop.dtype in (torch.float64, torch.float32) and z_prop.is_contiguous():
+                try:
+                    return logq_z(z_prop, logj_new)
+                except Exception as exc:  # a row shape the premapped kernel does not take: the round trip from here on
+                    logger.info("log q from the preconditioned coordinate is not available: %s", exc)
+                    logq_z = None
+            return self._flow_log_prob(x_prop)
+
+        return flow_lq, getattr(logq_z, "fused_args", None)
+
+    def _steps_callables(self, m):
+        """Arbitrary callables, and every chain in a preconditioned space: densities between the propose and accept halves
+        (`_pcn_split_steps`; the exchange hook of sharded runs is already installed, so the host enqueues step t + 1 while step
+        t runs), or one host round trip per step."""
+        e, T = self.engine, m.T
+        log_q, fused = None, None
+        if T is not None:
+            log_q, fused_args = self._flow_log_q_from(T)
+            # inverse transform (and log q, when it is available from z') inside the propose kernel where the transform has
+            # one bounded stage and nothing periodic
+            if (self.sampler_kwargs.get("fuse_transform", True) and hasattr(e, "pcn_ysplit_propose_tr") and hasattr(T, "_tables")
+                    and not np.any(getattr(T, "_periodic", [1]))):
+                td = T._tables()[1]
+                if td.hints & 7 in (5, 3):  # ASMC_TR_NO_PERIODIC | NO_PROBIT (logit) / NO_LOGIT (probit)
+                    fused = (td, fused_args)
+        common = dict(beta=m.beta, seed=m.seed, n_steps=m.n_steps, target=m.target, n_global=m.n_global, gid0=m.gid0, step0=m.step0,
+                      logj=m.logj)
+
+        def densities(z_prop, inverted=None):
+            return self._proposal_densities(z_prop, T, m.x_dtype, log_q, inverted)
+
+        if hasattr(e, "pcn_split_begin") and m.on_device:
+            counts, in_session = self._pcn_split_steps(m.z, m.ll, m.lp, m.lq, m.ref, m.st, densities, noise=m.noise, fused=fused,
+                                                       **common)
+            path = ("callables: whitened-state session (asmc_pcn_ysplit_*)" if in_session else
+                    "callables: split propose / accept with the step closed on the stream (asmc_pcn_split_*)")
+        else:
+            counts = self._pcn_round_trip_steps(m.z, m.ll, m.lp, m.lq, m.ref, m.st, densities, **common)
+            path = "callables: split propose / accept, one host round trip per step"
+        self.last_mutation_path = path if T is None else "preconditioned chain (z = T(x)): split propose / accept around the transform"
+        return (counts / m.n_global).tolist()
+
+    def _finish_mutation(self, m, acc_rates):
         """Bookkeeping behind every path: step counter, history, the NaN check of the carried log q, the wrapped population."""
-        e, comm = self.engine, self.comm
-        (particles, x, ll, lp, lq, beta, n_steps, target, noise, mu, L, Linv, st, seed, step0, acc_rates, dev_flow, on_device,
-         n_local, n_global, gid0, nu) = m
-        st["step"] = step0 + n_steps
+        e, comm, st = self.engine, self.comm, m.st
+        st["step"] = m.step0 + m.n_steps
         self.history.mcmc_acceptance.append(float(np.mean(acc_rates)))
         self.history.mcmc_step_size.append(float(st["rho"]))
         # the device-side loops count the NaNs of the carried log q themselves and return the count with their results
-        n_nan = e.pcn_lq_nan() if st.pop("lq_checked", False) else e.count_nonfinite(lq)[0]
+        n_nan = e.pcn_lq_nan() if st.pop("lq_checked", False) else e.count_nonfinite(m.lq)[0]
         # Sharded runs: every rank must take the same decision, which costs a collective and a synchronisation per
         # temperature.  While another importance step follows, its beta search counts the NaN weights of ALL ranks in the
         # records it exchanges anyway and raises there ("Log weights contain NaN values"); only the last mutation asks the ranks.
-        deferred = comm.sharded and beta < 1.0 and self.adaptive and self.device_bisection
+        # (A preconditioned chain asks at every temperature.)
+        deferred = comm.sharded and m.beta < 1.0 and self.adaptive and self.device_bisection and m.T is None
         pre = st.pop("prewrapped", None)
         if not deferred and self._global_counts([n_nan])[0]:
             raise ValueError("Log proposal contains NaN values")
-        return pre if pre is not None else self._wrap(x, ll, lp, lq, beta, like=particles)
+        if pre is not None:
+            return pre
+        x = m.z if m.T is None else e.asarray(m.T.inverse(m.z)[0], dtype=m.x_dtype)
+        return self._wrap(x, m.ll, m.lp, m.lq, m.beta, like=m.particles)
 
 
 _BLAS_CONTROLLER = []  # the process's ThreadpoolController, discovered once (the discovery walks every loaded library: ~1 ms)
@@ -1057,10 +928,3 @@ def _single_threaded_blas():
         import contextlib
 
         return contextlib.nullcontext()
-
-
-def pcn_adapt(rho: float, acc: float, target: float, t: int) -> float:
-    """Step-size adaptation of this repository's pCN spec, identical to the device
-    version in k_pcn_adapt: log rho += (acc - target)/(t+1)^0.75, rho clipped to [1e-4, 0.99]."""
-    r = math.exp(math.log(rho) + (acc - target) / (t + 1) ** 0.75)
-    return min(max(r, 1e-4), 0.99)

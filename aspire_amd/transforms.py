@@ -297,7 +297,7 @@ class FlowPreconditioningTransform:
     current particles and the Markov chain runs in its latent space, z = flow(T(x)) with T the composite data transform
     (periodic / bounded / affine stages) the reference puts in front of the flow.  The flow is one of this package's
     (`flow_backend` "coupling" or "maf"; zuko is absent); its passes and its training run in PyTorch, the composite stages on
-    the engine.  `HipSMC._mutate_preconditioned` drives it through the split propose / accept kernels like any user transform."""
+    the engine.  `HipSMC.mutate` drives it through the split propose / accept kernels like any user transform."""
 
     def __init__(self, parameters: list, flow_backend: str = "coupling", prior_bounds: dict | None = None,
                  bounded_to_unbounded: bool = True, bounded_transform: str = "probit", affine_transform: bool = True,

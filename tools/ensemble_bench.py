@@ -36,13 +36,9 @@ def bench(eng, name, n, d, steps):
     move_set = parse_moves(MOVES[name])
     schedule = move_set.schedule(seed, steps + 3)
 
-    def densities(y):
-        lq_new = sp._flow_log_prob(y)
-        lp_new, ll_new = sp._eval_prior_likelihood(y, lq_new)
-        return ll_new, lp_new, lq_new, None
-
     def step(t, tc):
-        run_step(eng, move_set.specs[schedule[tc]], d, x, beta, ll, lp, lq, None, densities, seed, 0, t, tc)
+        run_step(eng, move_set.specs[schedule[tc]], d, x, beta, ll, lp, lq, None,
+                 lambda y: sp._proposal_densities(y, None, x.dtype)[1:], seed, 0, t, tc)
 
     for t in range(3):
         step(t, t)

@@ -16,6 +16,7 @@ from conftest import random_coupling_flow  # noqa: E402
 
 from aspire_amd.engine import HipEngine  # noqa: E402
 from aspire_amd.flows import GaussianFlow  # noqa: E402
+from aspire_amd.moves import MoveSpec, run_step  # noqa: E402
 from aspire_amd.samplers.emcee_smc import HipEmceeSMC  # noqa: E402
 from aspire_amd.targets import DiagGaussianMixture  # noqa: E402
 
@@ -30,12 +31,10 @@ def bench(eng, kind, n, d, steps):
     lp, ll = sp._eval_prior_likelihood(x, lq)
     beta, seed = 0.5, 12345
 
+    spec = MoveSpec("stretch", 2, 2.0)
+
     def step(t, tc):
-        for h in (0, 1):
-            y, logf = eng.stretch_propose(x, h, 2.0, seed, 0, t, tc)
-            lq_new = sp._flow_log_prob(y)
-            lp_new, ll_new = sp._eval_prior_likelihood(y, lq_new)
-            eng.stretch_accept(x, h, y, logf, beta, ll, lp, lq, ll_new, lp_new, lq_new, seed, 0, t, tc)
+        run_step(eng, spec, d, x, beta, ll, lp, lq, None, lambda y: sp._proposal_densities(y, None, x.dtype)[1:], seed, 0, t, tc)
 
     for t in range(3):
         step(t, t)
